@@ -14,6 +14,13 @@ baseline (the oracle, i.e. a single-threaded port of the reference CPU path, on 
 timed steps run; `roofline.peak_sustained` = the compress probe held for 1.5 s with the same sampler on.
 Multi-GPU (launched by torch.distributed.run): independent proofs shard across ranks with no data-path collective
 ("replicas") -> weak scaling; only the timing uses a collective (MAX over ranks).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: model setup, W warm-up steps, the K
+timed steps, and the JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed
+step). Everything described above beyond that (single-proof latency, verification and golden sha256 of the last step, clock
+sampling, roofline, CNN-264k, CPU baseline, the 2^24 / 2^26 sumchecks, seam level, the batch-64 anchor, the transformer layer, the
+sharded sumcheck and per-rank figures of an N > 1 run) runs with `--full`; the --no-* options trim a full run.
+`--dump-outputs DIR` writes what the last timed step returned (proofs and model outputs) to DIR/*.npy (dump_outputs).
 """
 import argparse
 import json
@@ -42,6 +49,10 @@ GOLDEN = {"dense_4m": "dense4m_proof.json", "cnn_264k": "cnn264k_proof.json"}
 MIN_HOST_THREADS_PER_RANK = 3  # proving threads per rank below which a multi-GPU run is flagged host-bound (each rank also wants 2 CPUs for the HIP runtime)
 GOLDEN_SLOT = 7  # index inside the last timed step at which the golden input is proved
 SHARDED_WATCHDOG_S = float(os.environ.get("DP_BENCH_SHARDED_WATCHDOG_S", "240"))
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: the arrays of all files together (with the .npy headers still under 64 MB)
+DUMP_SEED = 0x5EED  # the fixed choice of sampled proof words and whole proofs
+DUMP_SAMPLE_WORDS = 256  # words sampled from every proof (fewer when the step holds very many proofs)
+DUMP_WHOLE_PROOFS = 3  # at most this many whole proofs, the golden slot's first
 PUBLISHED = {"dense_4m": 1000.0 / 2335.0, "cnn_264k": 1000.0 / 1242.0}  # reference README.md:17-18 (hardware unstated)
 WORKLOADS = {
     "dense_4m": "Dense-4M MLP (mlp.py --num-dense 5 --layer-width 1024: 4->1024->1024x4->3, Dense+Requant+ReLU blocks, 4.21M params), 1 input per proof",
@@ -183,11 +194,11 @@ class ClockSampler:
                 "power_w": col("power_uw", 1e-6), "busy_pct": col("busy_pct", 1.0), "temp_c": col("temp_mc", 1e-3)}
 
 
-def timed_region(prove_batch, my_inputs, conc, steps, warmup, dist=None, device_sync=None, reduce_device="cpu"):
+def timed_region(prove_batch, my_inputs, conc, steps, warmup, dist=None, device_sync=None, reduce_device="cpu", sample_clocks=True):
     """W untimed warm-up steps, then exactly K timed steps bracketed by barrier + device sync on both sides; returns
     (MAX over ranks of the elapsed seconds, result of the last step). A step = one batch of `conc` proofs (`conc` here is
-    the batch size of a step; how many of them are in flight at once is the prover's business)."""
-    import torch
+    the batch size of a step; how many of them are in flight at once is the prover's business). `sample_clocks`: run the
+    ClockSampler over the timed steps (timed_region.clocks; None without it)."""
 
     def barrier():
         if dist is not None:
@@ -198,7 +209,7 @@ def timed_region(prove_batch, my_inputs, conc, steps, warmup, dist=None, device_
     for i in range(warmup):
         prove_batch(my_inputs[i * conc:(i + 1) * conc])
     barrier()
-    sampler = ClockSampler(int(os.environ.get("LOCAL_RANK", "0"))).start()
+    sampler = ClockSampler(int(os.environ.get("LOCAL_RANK", "0"))).start() if sample_clocks else None
     t0 = time.perf_counter()
     last = None
     marks = [t0]
@@ -209,9 +220,10 @@ def timed_region(prove_batch, my_inputs, conc, steps, warmup, dist=None, device_
         marks.append(time.perf_counter())  # (diagnostics only: the measurement is the bracket around all K steps)
     barrier()
     elapsed = time.perf_counter() - t0
-    timed_region.clocks = sampler.stop()
+    timed_region.clocks = sampler.stop() if sampler is not None else None
     timed_region.step_ms = [round(1000 * (b - a), 1) for a, b in zip(marks, marks[1:])]
     if dist is not None:
+        import torch  # (only the MAX over ranks needs it: a single-GPU run need not import torch)
         te = torch.tensor([elapsed], dtype=torch.float64, device=reduce_device)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
@@ -289,9 +301,10 @@ def transformer_layer_section(dpa, dev, conc=320):  # (round 3: 64 in flight 87 
     return r
 
 
-def measure_workload(dpa, dev, workload, conc, steps, warmup, world, rank, dist, torch, profile=False, strong_batch=0):
-    """setup + latency of one proof + the timed throughput region + verification of the last batch (+ the per-kernel HIP
-    event profile of one more proof); the model context and its workers are released before returning"""
+def measure_workload(dpa, dev, workload, conc, steps, warmup, world, rank, dist, torch, profile=False, strong_batch=0, full=True, dump_dir=None):
+    """setup + the timed throughput region; with `full` also latency of one proof, clocks over the timed steps, verification
+    and golden check of the last batch (+ the per-kernel HIP event profile of one more proof). `dump_dir`: the last timed
+    step's result goes there (dump_outputs). The model context and its workers are released before returning."""
     import numpy as np
     mb = make_model(dpa, workload)
     t0 = time.time()
@@ -313,20 +326,30 @@ def measure_workload(dpa, dev, workload, conc, steps, warmup, world, rank, dist,
     gslot = min(GOLDEN_SLOT, batch - 1)
     if gold is not None and batch:
         my_inputs[lo_last + gslot] = mb.input(gold["input_index"])
+    # one proof alone first, in every run: it records the model's footprint, from which the first batch sizes its workers' arenas and
+    # with them how many proofs fit in flight (dp_model_prove_batch; with nothing proved yet a worker gets 1.5 GB instead of 336 MB)
     t0 = time.perf_counter()
     prover.prove(my_inputs[0])
     first_ms = 1000 * (time.perf_counter() - t0)
-    lat = []
-    for _ in range(3):  # the single-proof figure is the median of three (one sample caught a 40 ms host hiccup in round 2)
-        t0 = time.perf_counter()
-        prover.prove(my_inputs[0])
-        lat.append(1000 * (time.perf_counter() - t0))
-    latency_ms = sorted(lat)[1]
+    latency_ms, lat = None, []
+    if full:
+        for _ in range(3):  # the single-proof figure is the median of three (one sample caught a 40 ms host hiccup in round 2)
+            t0 = time.perf_counter()
+            prover.prove(my_inputs[0])
+            lat.append(1000 * (time.perf_counter() - t0))
+        latency_ms = sorted(lat)[1]
     cuda = torch.cuda.is_available() and (dist is None or dist.get_backend() == "nccl")
     elapsed, last = timed_region(lambda xs: prover.prove_batch(xs, conc), my_inputs, batch, steps, warmup, dist,
-                                 torch.cuda.synchronize if cuda else None, "cuda" if cuda else "cpu")
+                                 torch.cuda.synchronize if cuda else None, "cuda" if cuda else "cpu", sample_clocks=full)
     step_ms = list(getattr(timed_region, "step_ms", []))
     clocks = getattr(timed_region, "clocks", None)
+    if dump_dir and batch:
+        dump_outputs(dump_dir, last[0], last[1], gslot if gold is not None else 0)
+    if not full:
+        in_flight = prover.in_flight()
+        proof_words = int(last[0][0].size) if batch else 0
+        ctx.free()
+        return dict(mb=mb, elapsed=elapsed, setup_s=setup_s, proof_words=proof_words, step_ms=step_ms, in_flight=in_flight)
     # EVERY proof of the last step must verify — an invalid proof voids the measurement. One proof through the host-only
     # verifier (dp_verify, the latency figure: protocol checks on one thread, its Merkle paths on up to 8, DP_VERIFY_THREADS), then the whole step through dp_verify_batch: protocol checks on the host
     # threads, the Merkle paths of each proof (125 000 compress() for Dense-4M) authenticated on the GPU in one launch.
@@ -350,6 +373,47 @@ def measure_workload(dpa, dev, workload, conc, steps, warmup, world, rank, dist,
     ctx.free()  # releases the workers' arenas too: the next workload sizes its own against the free HBM
     return dict(mb=mb, elapsed=elapsed, latency_ms=latency_ms, latency_samples_ms=[round(v, 2) for v in lat], first_ms=first_ms, setup_s=setup_s, proof_words=int(last[0][0].size),
                 verified=checked, step_ms=step_ms, verify_ms=round(1000 * one, 2), verify_batch_ms_per_proof=round(vb_ms / max(1, checked), 3), in_flight=in_flight, kernel_report=rep, golden_ok=golden_ok, clocks=clocks)
+
+
+def _u64_halves(words):
+    """u64 words -> float64 [..., 2] = (low, high) 32-bit halves: exact (a float64 holds every 32-bit integer), where one float64 per
+    Goldilocks word would round"""
+    import numpy as np
+    w = np.asarray(words, dtype=np.uint64)
+    return np.stack([(w & np.uint64(0xFFFFFFFF)).astype(np.float64), (w >> np.uint64(32)).astype(np.float64)], axis=-1)
+
+
+def dump_outputs(out_dir, proofs, outputs, golden_slot=0):
+    """--dump-outputs: what Prover.prove_batch returned for the last timed step, as float64 .npy files under DUMP_BUDGET_BYTES:
+      outputs.npy                  [proofs, nout]  every model output of the step (quantised integers, exact)
+      proof_words.npy              [proofs]        the length of every proof in u64 words
+      proof_sample_positions.npy   [m]             m word positions, a fixed seeded choice below the shortest proof's length
+      proof_sample.npy             [proofs, m, 2]  the words of every proof at those positions, as (low, high) 32-bit halves
+      proof_slot<i>.npy            [words, 2]      whole proofs of slot i, as (low, high) halves: the golden input's slot first, then
+                                                   a seeded choice of others, at most DUMP_WHOLE_PROOFS and while the budget lasts
+    The inputs of a step are the same from run to run, so two builds compare file for file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(proofs)
+    rng = np.random.default_rng(DUMP_SEED)
+    lens = np.array([p.size for p in proofs], dtype=np.float64)
+    files = {"outputs": np.asarray(outputs).astype(np.float64), "proof_words": lens}
+    left = DUMP_BUDGET_BYTES - sum(a.nbytes for a in files.values())
+    shortest = int(lens.min())
+    m = max(1, min(DUMP_SAMPLE_WORDS, shortest, left // 2 // (16 * n + 8)))  # the sample takes at most half of what is left
+    pos = np.sort(rng.choice(shortest, size=m, replace=False))
+    files["proof_sample_positions"] = pos.astype(np.float64)
+    files["proof_sample"] = _u64_halves(np.stack([p[pos] for p in proofs]))
+    left -= files["proof_sample_positions"].nbytes + files["proof_sample"].nbytes
+    slots = [golden_slot] + [int(i) for i in rng.permutation(n) if i != golden_slot]
+    for i in slots[:DUMP_WHOLE_PROOFS]:
+        if 16 * proofs[i].size > left:
+            break
+        files[f"proof_slot{i}"] = _u64_halves(proofs[i])
+        left -= files[f"proof_slot{i}"].nbytes
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(files)
 
 
 def cnn_steps(steps):
@@ -467,17 +531,23 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="BASELINE config 4: ONE fixed batch of this many proofs per step, split over the ranks (strong scaling); "
                                                          "0 = the default weak-scaling run (fixed work per GPU)")
     ap.add_argument("--concurrency", type=int, default=0, help=f"independent proofs in flight per GPU (0 = {DEFAULT_IN_FLIGHT})")
+    ap.add_argument("--full", action="store_true", help="every side measurement and check besides the headline: single-proof latency, verification and golden sha256 of the "
+                                                        "last step, clocks, roofline, CNN-264k, CPU baseline, 2^24 / 2^26 sumchecks, seam level, batch-64 anchor, transformer layer, "
+                                                        "the sharded sumcheck and per-rank figures of an N > 1 run (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the proofs and model outputs of the last timed step to DIR/*.npy (float64, < 64 MB; dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher — one rank per GPU under torch.distributed.run
         # (the driver's multi-GPU command line does this itself; a plain invocation used to die on the WORLD_SIZE assert below)
         return spawn_ranks(args.gpus)
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")  # one hardware queue per in-flight proof stream, as many as the GPU serves without time slicing
-    if os.environ.get("DP_BENCH_NO_TORCH") and int(os.environ.get("WORLD_SIZE", "1")) == 1:
-        # quick single-GPU checks on a fresh box, where the first `import torch` alone costs 1-2 minutes: no barrier is needed
-        # at N=1 and every prove_batch returns only when its proofs are complete and downloaded, so the device is idle at both
-        # ends of the timed region without torch.cuda.synchronize()
+    if (os.environ.get("DP_BENCH_NO_TORCH") or not args.full) and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+        # a plain single-GPU run (and any run with DP_BENCH_NO_TORCH) skips torch, whose first import on a fresh machine alone
+        # costs 1-2 minutes: no barrier is needed at N=1 and every prove_batch returns only when its proofs are complete and
+        # downloaded, so the device is idle at both ends of the timed region without torch.cuda.synchronize()
         class torch:  # noqa: N801
             class cuda:  # noqa: N801
                 is_available = staticmethod(lambda: False)
@@ -529,13 +599,14 @@ def main():
     conc = args.concurrency if args.concurrency > 0 else DEFAULT_IN_FLIGHT
 
     dev = dpa.Device(local_rank)
-    main_w = measure_workload(dpa, dev, args.workload, conc, args.steps, args.warmup, world, rank, dist, torch, profile=rank == 0, strong_batch=args.batch)
+    main_w = measure_workload(dpa, dev, args.workload, conc, args.steps, args.warmup, world, rank, dist, torch, profile=rank == 0 and args.full, strong_batch=args.batch,
+                              full=args.full, dump_dir=args.dump_outputs if rank == 0 else None)
     cnn_w = None
-    if args.workload == "dense_4m" and not args.no_cnn and not args.batch:
+    if args.full and args.workload == "dense_4m" and not args.no_cnn and not args.batch:
         cnn_w = measure_workload(dpa, dev, "cnn_264k", conc, cnn_steps(args.steps), min(1, args.warmup), world, rank, dist, torch)
 
     per_rank = None
-    if dist is not None and world > 1:  # what every rank saw: a slow rank (setup, one long step) must be visible in the N > 1 line
+    if args.full and dist is not None and world > 1:  # what every rank saw: a slow rank (setup, one long step) must be visible in the N > 1 line
         mine = {"rank": rank, "step_ms": [round(v, 1) for v in main_w["step_ms"]], "setup_s": round(main_w["setup_s"], 2), "single_proof_latency_ms": round(main_w["latency_ms"], 2),
                 "host_threads": host_threads, "in_flight": int(main_w["in_flight"])}
         per_rank = [None] * world
@@ -543,11 +614,29 @@ def main():
             dist.all_gather_object(per_rank, mine)
         except Exception as e:  # noqa: BLE001
             per_rank = [mine, {"error": f"all_gather_object: {type(e).__name__}: {e}"[:200]}]
+    def rate(w, steps):
+        return (steps * args.batch if args.batch else world * steps * BATCHES_PER_STEP * conc) / w["elapsed"]
     result = None
-    if rank == 0:
-        def rate(w, steps):
-            return (steps * args.batch if args.batch else world * steps * BATCHES_PER_STEP * conc) / w["elapsed"]
+    if rank == 0:  # the headline, in every run
         value = rate(main_w, args.steps)
+        result = {
+            "metric": {"dense_4m": "proofs/sec (prover), Dense-4M", "cnn_264k": "proofs/sec (prover), CNN-264k"}.get(args.workload, "proofs/sec (prover), MLP-w256"),
+            "value": round(value, 4), "unit": "proofs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(1000.0 * main_w["elapsed"] / args.steps, 3), "step_ms_min_median_max": ([min(main_w["step_ms"]), sorted(main_w["step_ms"])[len(main_w["step_ms"]) // 2], max(main_w["step_ms"])] if main_w["step_ms"] else None), "higher_is_better": True, "scaling": "strong" if args.batch else "weak",
+            "vs_baseline": round(value / PUBLISHED[args.workload], 3) if args.workload in PUBLISHED else None,
+            "baseline_note": "reference README.md:17-18 proving times (Dense-4M 2335 ms, CNN-264k 1242 ms) on unstated CPU hardware",
+            "dtype": "u64", "data": "synthetic", "full": bool(args.full),
+            "config": {"workload": WORKLOADS[args.workload], "arithmetic": "Goldilocks p = 2^64 - 2^32 + 1 and its degree-2 extension (canonical u64 words)",
+                       "proofs_per_step_per_gpu": (strong_share(args.batch, world, 0) if args.batch else BATCHES_PER_STEP * conc), "proofs_in_flight_per_gpu": main_w["in_flight"],
+                       "proofs_per_step_all_gpus": (args.batch if args.batch else world * BATCHES_PER_STEP * conc),
+                       "strong_scaling_note": (f"BASELINE config 4: one batch of {args.batch} independent proofs per step split over {world} GPU(s) (rank r proves proofs r, r+{world}, ...); "
+                                               "every rank commits the model itself (Context::generate recomputed per rank, outside the timed region), no data-path collective") if args.batch else None,
+                       "host_cpu_budget": budget, "host_threads_per_rank": host_threads, "host_bound": bool(host_bound), "min_cpus_per_gpu": MIN_HOST_THREADS_PER_RANK + 2,
+                       "parallelism": f"replicas x{world} GPUs x {main_w['in_flight']} proofs in flight per GPU in lock-step cohorts of {os.environ.get('DP_COHORT') or -(-main_w['in_flight'] // 22)} (independent proofs, no data-path collective)",
+                       "proof_words": main_w["proof_words"], "setup_s": round(main_w["setup_s"], 2),
+                       "env_knobs": {k: v for k, v in sorted(os.environ.items()) if k.startswith("DP_") or k == "GPU_MAX_HW_QUEUES"}, "device": dev.name},
+        }
+    if rank == 0 and args.full:
         # ---- roofline. The proof is integer work with no dense contraction (MFMA unused by design). Its chip-filling work is
         # Poseidon2: every Merkle node is one compress() = 2 permutations = ~1040 Goldilocks multiplications for 96 B moved
         # (10.8 mul/B: VALU-integer bound, HBM irrelevant), so the roofline is priced in compress()/s against the rate the same
@@ -626,28 +715,14 @@ def main():
                    "baseline_note": "reference README.md:17 CNN-264k proving time 1242 ms on unstated CPU hardware",
                    "workload": WORKLOADS["cnn_264k"], "proof_words": cnn_w["proof_words"], "setup_s": round(cnn_w["setup_s"], 2), "verified": True, "golden_sha256_ok": cnn_w["golden_ok"], "verified_proofs_of_last_step": cnn_w["verified"], "verify_batch_ms_per_proof": cnn_w["verify_batch_ms_per_proof"],
                    "cpu_baseline": None if (world > 1 or args.no_cpu_baseline) else cpu_baseline(cnn_w["mb"], "cnn_264k")}
-        result = {
-            "metric": {"dense_4m": "proofs/sec (prover), Dense-4M", "cnn_264k": "proofs/sec (prover), CNN-264k"}.get(args.workload, "proofs/sec (prover), MLP-w256"),
-            "value": round(value, 4), "unit": "proofs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1000.0 * main_w["elapsed"] / args.steps, 3), "step_ms_min_median_max": ([min(main_w["step_ms"]), sorted(main_w["step_ms"])[len(main_w["step_ms"]) // 2], max(main_w["step_ms"])] if main_w["step_ms"] else None), "higher_is_better": True, "scaling": "strong" if args.batch else "weak",
-            "vs_baseline": round(value / PUBLISHED[args.workload], 3) if args.workload in PUBLISHED else None,
-            "baseline_note": "reference README.md:17-18 proving times (Dense-4M 2335 ms, CNN-264k 1242 ms) on unstated CPU hardware",
-            "dtype": "u64", "data": "synthetic",
-            "config": {"workload": WORKLOADS[args.workload], "arithmetic": "Goldilocks p = 2^64 - 2^32 + 1 and its degree-2 extension (canonical u64 words)",
-                       "proofs_per_step_per_gpu": (strong_share(args.batch, world, 0) if args.batch else BATCHES_PER_STEP * conc), "proofs_in_flight_per_gpu": main_w["in_flight"],
-                       "proofs_per_step_all_gpus": (args.batch if args.batch else world * BATCHES_PER_STEP * conc),
-                       "strong_scaling_note": (f"BASELINE config 4: one batch of {args.batch} independent proofs per step split over {world} GPU(s) (rank r proves proofs r, r+{world}, ...); "
-                                               "every rank commits the model itself (Context::generate recomputed per rank, outside the timed region), no data-path collective") if args.batch else None,
-                       "single_proof_latency_ms": round(main_w["latency_ms"], 2), "single_proof_latency_samples_ms": main_w["latency_samples_ms"], "first_proof_ms": round(main_w["first_ms"], 2),
-                       "host_cpu_budget": budget, "host_threads_per_rank": host_threads, "host_bound": bool(host_bound),
-                       "gpu_clocks_timed_region": main_w.get("clocks"),
-                       "min_cpus_per_gpu": MIN_HOST_THREADS_PER_RANK + 2, "per_rank": per_rank,
-                       "parallelism": f"replicas x{world} GPUs x {main_w['in_flight']} proofs in flight per GPU in lock-step cohorts of {os.environ.get('DP_COHORT') or -(-main_w['in_flight'] // 22)} (independent proofs, no data-path collective)",
-                       "proof_words": main_w["proof_words"], "setup_s": round(main_w["setup_s"], 2), "verified": True, "golden_sha256_ok": main_w["golden_ok"], "verified_proofs_of_last_step": main_w["verified"], "verify_ms_per_proof": main_w["verify_ms"], "verify_batch_ms_per_proof": main_w["verify_batch_ms_per_proof"],
-                       "env_knobs": {k: v for k, v in sorted(os.environ.items()) if k.startswith("DP_") or k == "GPU_MAX_HW_QUEUES"}, "device": dev.name},
+        result["config"].update({
+            "single_proof_latency_ms": round(main_w["latency_ms"], 2), "single_proof_latency_samples_ms": main_w["latency_samples_ms"], "first_proof_ms": round(main_w["first_ms"], 2),
+            "gpu_clocks_timed_region": main_w.get("clocks"), "per_rank": per_rank,
+            "verified": True, "golden_sha256_ok": main_w["golden_ok"], "verified_proofs_of_last_step": main_w["verified"], "verify_ms_per_proof": main_w["verify_ms"], "verify_batch_ms_per_proof": main_w["verify_batch_ms_per_proof"]})
+        result.update({
             "roofline": roofline, "cpu_baseline": cpu, "cnn_264k": cnn, "sumcheck24": sc24, "sumcheck24_sharded": None,
             "seam_level": None if (world > 1 or args.no_seam_level) else seam_level(host_threads, batch_rate=value),
-        }
+        })
         result["tail_roofline"] = tail_roofline()
         if sc24 is not None and not args.batch:
             # the size sumcheck/benches/devirgo_sumcheck.rs itself runs, on ONE GPU: the anchor of the sharded 2^26 run (`sumcheck26_sharded` of an N > 1 line; the model of
@@ -678,7 +753,7 @@ def main():
     # BASELINE config 5 across the ranks: ONE 2^24 sumcheck, every rank owns a contiguous 1/N slice of each table and the
     # per-round shares are all-gathered over RCCL (deep_prove_amd/sharded.py). It runs AFTER the headline is complete and
     # under a watchdog: neither an exception nor a collective that never returns may take the JSON line down.
-    if world > 1 and not args.no_sumcheck24:
+    if args.full and world > 1 and not args.no_sumcheck24:
         def give_up():
             if rank == 0:
                 result["sumcheck24_sharded"] = {"error": f"no result within {SHARDED_WATCHDOG_S:.0f} s (watchdog)"}

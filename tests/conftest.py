@@ -8,6 +8,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+# Every shard of a sharded sumcheck (and every proof in flight) owns a stream whose persistent kernels wait for the host; two
+# such streams must never share a hardware queue (deep-prove_amd/_lib.py). The library sets GPU_MAX_HW_QUEUES=24 only when the
+# variable is unset, so an environment that presets a smaller count (HIP's default is 4) let the 4-shard tests of
+# test_gpu_sharded.py queue one shard's kernel behind another's persistent wait. The suite runs with the count the library is
+# built for; it must be in place before the first HIP call of the process.
+try:
+    _queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "0"))
+except ValueError:
+    _queues = 0
+if _queues < 24:
+    os.environ["GPU_MAX_HW_QUEUES"] = "24"
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")

@@ -2,7 +2,7 @@
 # r06 final: everything the driver line quotes, collected on the FINAL sources (every file carries tools/srchash.py's hash and bench.py refuses figures from
 # other sources): 1. the GPU suite; 2. FETCH_SIZE / WRITE_SIZE passes (separate runs, as MI355X_MICROARCH.md prescribes) of three latency-mode Dense-4M
 # proofs and of the 2^24 sumcheck; 3. the SQ instruction pass of the cohort regime + the compress probe; 4. the member timing of the diagnostic builds
-# (entry -> exit, and the permutation count) -> tail_roofline; 5. rocprofv3 --kernel-trace --stats of the cohort regime; 6. the default bench.
+# (entry -> exit, and the permutation count) -> tail_roofline; 5. rocprofv3 --kernel-trace --stats of the cohort regime; 6. the full bench (bench.py --full).
 N=${N:-704}  # proofs in flight of the cohort regime that is profiled = bench.py's default
 o=gpurun_out/r06_final; mkdir -p $o; export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
@@ -76,7 +76,7 @@ timeout -s KILL 200 python tools/archive/latency_probe.py cnn_264k > $o/lat_cnn.
 DP_TIMING=2 timeout -s KILL 200 python tools/archive/latency_probe.py > $o/lat_t2.txt 2>&1; grep -E "sc-debug|sumcheck rounds" $o/lat_t2.txt | tail -2 | cut -c1-260
 ( for f in default_1 lp4096_1 hostmail_1 nopin_1 default_2 lp4096_2 hostmail_2 nopin_2; do echo "$f: $(grep -E 'proof [3-5]' $o/lat_$f.txt | sed 's/.*library //' | tr '\n' ' ')"; done; echo "cnn_264k: $(grep -E 'proof [3-5]' $o/lat_cnn.txt | sed 's/.*library //' | tr '\n' ' ')"; grep -E "sc-debug|sumcheck rounds" $o/lat_t2.txt | tail -2 ) > $o/r06_latency_ab.txt
 step "bench"
-timeout -s KILL 1500 python bench.py > $o/bench.json 2> $o/bench.err; echo "bench rc=$?"; tail -3 $o/bench.err | cut -c1-300
+timeout -s KILL 1500 python bench.py --full > $o/bench.json 2> $o/bench.err; echo "bench rc=$?"; tail -3 $o/bench.err | cut -c1-300
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r06_final/bench.json').read().strip().split('\n')[-1])
