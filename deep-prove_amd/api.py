@@ -564,6 +564,11 @@ class Context:
         check(_lib.load().dp_model_verifier_blob(self.h, C.byref(pw), C.byref(pn)))
         return _take(pw, pn.value)
 
+    def infer(self, inputs_i64):
+        """dp_model_infer: Model::run for every row of inputs_i64[n, ninput] on this context's GPU; returns (outputs[n, nout], wall_ms)"""
+        from .infer import infer
+        return infer(self, inputs_i64)
+
     def free(self):
         if self.h:
             _lib.load().dp_model_free(self.h)

@@ -1,9 +1,12 @@
 // extern "C" surface of libdeepprove_hip.so (declared in include/deep_prove_hip.h).
 #include "../../include/deep_prove_hip.h"
+#include "../../include/deep_prove_hip_infer.h"
 #include "zkml.h"
 #include "blob.h"
 #include "sharded.h"
 #include "fiber.h"
+#define DP_INFER_PLANNER
+#include "infer.h"
 #include <dlfcn.h>
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>  // types and enums only: the functions are resolved with dlopen (no link-time dependency on librccl)
@@ -48,7 +51,9 @@ struct dp_batch_commit { DevBatchCommit c; };
 struct dp_model {
   dp_ctx* ctx; std::unique_ptr<Context> zk; std::vector<std::unique_ptr<Dev>> workers; std::vector<dp::Cohort*> cohorts;
   size_t last_in_flight = 0, in_flight_cap = 0; size_t prove_peak = 0;  // largest arena footprint a proof of this model has had so far (sizes the arenas of batch workers)
-  ~dp_model() { for (size_t i = cohorts.size(); i-- > 0;) hip_cohort_free(cohorts[i]); }  // (last first: a cohort that shares a stream goes before the one that owns it)
+  // dp_model_infer: the flattened model and its constants on the device, made at the first call (dp_model_setup allocates nothing for them)
+  std::unique_ptr<InferProgram> infer_prog; InferDeviceState* infer_state = nullptr;
+  ~dp_model() { for (size_t i = cohorts.size(); i-- > 0;) hip_cohort_free(cohorts[i]); if (infer_state) hip_infer_state_free(infer_state); }  // (last first: a cohort that shares a stream goes before the one that owns it)
 };
 
 // Every cohort stream needs a hardware queue of its own (24 are served without time slicing; the HIP runtime multiplexes streams
@@ -1362,6 +1367,21 @@ int32_t dp_model_infer_host(const int64_t* model_blob, size_t nwords, const int6
     const std::vector<int64_t> o = model_output(m, tr);
     DP_REQUIRE(*noutput >= o.size(), DP_ERR_ARG, "output buffer too small");
     memcpy(output, o.data(), o.size() * 8); *noutput = o.size();
+  });
+}
+int32_t dp_model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms) {
+  return guard([&] {
+    DP_REQUIRE(m && inputs && outputs && noutput, DP_ERR_ARG, "bad arguments");
+    const ModelSpec& spec = m->zk->model;
+    DP_REQUIRE(ninput == spec.input_len, DP_ERR_SHAPE, "input length mismatch");
+    CtxLock lk(m->ctx);
+    if (!m->infer_prog) m->infer_prog.reset(new InferProgram(infer_plan(spec)));  // (refuses LayerNorm / Softmax / Mha / GELU before any device work)
+    DP_REQUIRE(noutput_cap >= m->infer_prog->output_len, DP_ERR_ARG, "output buffer too small");
+    *noutput = m->infer_prog->output_len;
+    if (wall_ms) *wall_ms = 0;
+    if (!ninputs) return;
+    if (!m->infer_state) m->infer_state = hip_infer_state_new(m->ctx->device_id);
+    hip_infer_run(m->ctx->dev, *m->infer_prog, m->infer_state, inputs, ninputs, outputs, noutput_cap, wall_ms);
   });
 }
 int32_t dp_host_poseidon2(uint64_t state[8], int32_t force_scalar, int32_t* vectorised) {

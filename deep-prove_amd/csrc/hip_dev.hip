@@ -19,6 +19,7 @@
 #include "deleg_tail.h"
 #include "commit_tail.h"
 #include "sponge_host.h"
+#include "infer.h"
 #include <hip/hip_runtime.h>
 #include <sched.h>
 #include <sys/syscall.h>
@@ -2330,5 +2331,7 @@ void hip_dev_pcs_share(Dev* worker, Dev* owner) { static_cast<HipDev*>(worker)->
 void hip_dev_set_latency_mode(Dev* d, bool on) { static_cast<HipDev*>(d)->set_latency_mode(on); }
 void hip_dev_profile_enable(Dev* d, bool on) { static_cast<HipDev*>(d)->profile_enable(on); }
 std::string hip_dev_profile_report(Dev* d) { return static_cast<HipDev*>(d)->profile_report(); }
+
+#include "infer_kernels.inc"  // dp_model_infer: batched quantised inference (infer.h)
 
 }  // namespace dp

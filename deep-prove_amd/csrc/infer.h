@@ -1,0 +1,156 @@
+// Batched quantised inference on the device (dp_model_infer, include/deep_prove_hip_infer.h): Model::run for many independent inputs.
+// The host flattens a ModelSpec into an InferProgram (infer_plan below: tensors, constants, one op per launch) once per model; hip_infer_run
+// (infer_kernels.inc, compiled into hip_dev.hip) executes it for a batch: activations are [batch][tensor], one launch serves the whole batch.
+// Which products take the i8 MFMA is decided here, statically: the weights within -128..127, K * 128 * 128 < 2^31 and the input produced by
+// a Requant (through ReLU / MaxPool / Flatten) or a model input the host has range-checked at upload. Everything else is 64-bit multiply-add
+// with the host's wrap-around.
+#pragma once
+#include "dev.h"
+#include <cstdint>
+#include <vector>
+
+namespace dp {
+
+enum InferQ { IQ_NO = 0, IQ_YES = 1, IQ_IF_INPUTS = 2 };  // every value of the tensor within -128..127: never / always / iff the model inputs of the call are
+struct InferTensor { size_t len = 0; int q = IQ_NO; };
+// a constant of the model. h64 points into the ModelSpec (it lives as long as the dp_model); w8 = the same matrix as int8, transposed to [N][K]
+// (both operands of k_infer_gemm_i8 are read along K), empty when a weight does not fit. Uploaded at the first launch that reads it.
+struct InferConst { const int64_t* h64 = nullptr; size_t n = 0; std::vector<int8_t> w8; };
+enum InferOpKind { IO_GEMM = 0, IO_GEMM2, IO_REQUANT, IO_RELU, IO_ADDC, IO_ADD2, IO_EMBED, IO_MAXPOOL, IO_CONV, IO_KINDS };
+// out[b][c*sOc + r*sOr + n*sOn] = sum_m A[b][c*sAc + r*sAr + m*sAm] * B[(B a tensor: b)][c*sBc + m*sBm + n*sBn] (+ bias[n])
+struct InferGemmShape { size_t C = 1, R = 0, K = 0, N = 0; size_t sAc = 0, sAr = 0, sAm = 0, sBc = 0, sBm = 0, sBn = 0, sOc = 0, sOr = 0, sOn = 0; };
+struct InferOp {
+  int kind = IO_GEMM, node = 0;
+  int in0 = -1, in1 = -1, out = -1;  // tensors
+  int w = -1, bias = -1;             // constants
+  InferGemmShape g;                  // IO_GEMM (B = constant w; the i8 form when in0 is q and w has an int8 copy), IO_GEMM2 (B = tensor in1)
+  int64_t left = 1, right = 1;       // IO_ADDC: left * x + right * w[i]; IO_ADD2: left * a + right * b; IO_REQUANT: left = multiplier
+  unsigned shift = 0, bits = 0;      // IO_REQUANT
+  size_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // IO_EMBED: vocabulary, embedding size; IO_MAXPOOL: c, h, w; IO_CONV: kw, kx, real_nw, nw, unp_out[3]
+};
+struct InferProgram {
+  size_t input_len = 0, output_len = 0;
+  std::vector<InferTensor> tensors;
+  std::vector<int> inputs, outputs;  // tensor ids of the model's input / output tensors, in the order they are concatenated
+  std::vector<InferConst> consts;
+  std::vector<InferOp> ops;
+};
+struct InferDeviceState;  // the constants on the device (made at the first call, freed with the model)
+InferDeviceState* hip_infer_state_new(int device);
+void hip_infer_state_free(InferDeviceState* s);
+// inputs: ninputs x p.input_len words; outputs: ninputs x out_stride words (the first p.output_len of each row are written). Throws DpError.
+void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* inputs, size_t ninputs, int64_t* outputs, size_t out_stride, double* wall_ms);
+
+#ifdef DP_INFER_PLANNER  // (capi.cpp, after zkml.h)
+inline const char* infer_kind_name(int k) {
+  static const char* names[] = {"Dense", "Requant", "ReLU", "Conv", "MaxPool", "Flatten", "MatMul", "Add", "Embeddings", "Positional", "MatMul2", "Add2", "ConcatMatMul", "QKV", "LayerNorm", "Softmax", "Mha", "GELU"};
+  return k >= 0 && k < 18 ? names[k] : "unknown";
+}
+inline InferProgram infer_plan(const ModelSpec& m) {
+  for (size_t id = 0; id < m.layers.size(); id++) {
+    const int k = m.layers[id].kind;
+    DP_REQUIRE(k >= L_DENSE && k <= L_QKV, DP_ERR_ARG, "dp_model_infer: node " + std::to_string(id) + " is a " + infer_kind_name(k) + " layer (kind " + std::to_string(k) +
+               "): LayerNorm, Softmax, Mha and GELU are not inferred on the device yet");
+  }
+  InferProgram p;
+  p.input_len = m.input_len; p.output_len = model_output_len(m);
+  std::vector<size_t> lens; tensor_lens(m, lens);
+  auto new_tensor = [&](size_t len, int q) { InferTensor t; t.len = len; t.q = q; p.tensors.push_back(t); return (int)p.tensors.size() - 1; };
+  auto new_const = [&](const int64_t* h, size_t n) { InferConst c; c.h64 = h; c.n = n; p.consts.push_back(std::move(c)); return (int)p.consts.size() - 1; };
+  for (size_t n : input_tensor_lens(m)) p.inputs.push_back(new_tensor(n, IQ_IF_INPUTS));
+  std::vector<std::vector<int>> slot(m.layers.size());  // tensor of (node, output slot)
+  auto tensor_of = [&](const Edge& e) { return e.from < 0 ? p.inputs.at((size_t)e.slot) : slot.at((size_t)e.from).at((size_t)e.slot); };
+  // the constant [K][N] matrix (b_is_nk: stored [N][K]) of a product, with its int8 copy [N][K] when every weight fits and K * 128 * 128 < 2^31
+  auto weight_const = [&](const int64_t* h, size_t K, size_t N, bool b_is_nk) {
+    const int c = new_const(h, K * N);
+    bool fits = (double)K * 128.0 * 128.0 < 2147483648.0;
+    for (size_t i = 0; i < K * N && fits; i++) fits = h[i] >= -128 && h[i] <= 127;
+    if (fits) {
+      std::vector<int8_t>& w8 = p.consts[(size_t)c].w8;
+      w8.resize(K * N);
+      for (size_t n = 0; n < N; n++) for (size_t k = 0; k < K; k++) w8[n * K + k] = (int8_t)(b_is_nk ? h[n * K + k] : h[k * N + n]);
+    }
+    return c;
+  };
+  auto const_gemm = [&](size_t id, int in, const int64_t* h, size_t s, size_t K, size_t N, bool b_is_nk, const int64_t* bias) {
+    InferOp o; o.kind = IO_GEMM; o.node = (int)id; o.in0 = in; o.out = new_tensor(s * N, IQ_NO);
+    o.w = weight_const(h, K, N, b_is_nk); o.bias = bias ? new_const(bias, N) : -1;
+    o.g.C = 1; o.g.R = s; o.g.K = K; o.g.N = N; o.g.sAr = K; o.g.sAm = 1; o.g.sBm = b_is_nk ? 1 : N; o.g.sBn = b_is_nk ? K : 1; o.g.sOr = N; o.g.sOn = 1;
+    p.ops.push_back(o);
+    return o.out;
+  };
+  for (size_t id = 0; id < m.layers.size(); id++) {
+    const LayerSpec& l = m.layers[id];
+    const std::vector<Edge> e = edges_in(m, id);
+    DP_REQUIRE(e.size() == in_degree(l), DP_ERR_SHAPE, "model graph: wrong number of inputs for a node");
+    const int a = tensor_of(e[0]);
+    const size_t alen = p.tensors[(size_t)a].len;
+    InferOp o; o.node = (int)id; o.in0 = a;
+    if (l.kind == L_FLATTEN) { slot[id] = {a}; continue; }
+    if (l.kind == L_DENSE) { DP_REQUIRE(alen == l.ncols, DP_ERR_SHAPE, "dense input size mismatch"); slot[id] = {const_gemm(id, a, l.weights.data(), 1, l.ncols, l.nrows, true, l.bias.data())}; continue; }
+    if (l.kind == L_MATMUL) {
+      DP_REQUIRE(l.nrows && alen % l.nrows == 0, DP_ERR_SHAPE, "matmul input size mismatch");
+      slot[id] = {const_gemm(id, a, l.weights.data(), alen / l.nrows, l.nrows, l.ncols, l.mm_transpose, l.bias.empty() ? nullptr : l.bias.data())};
+      continue;
+    }
+    if (l.kind == L_QKV) {
+      const size_t k = l.nrows, n = l.ncols;
+      DP_REQUIRE(k && alen % k == 0 && l.weights.size() == 3 * k * n && l.bias.size() == 3 * n, DP_ERR_SHAPE, "qkv: shapes");
+      for (size_t w = 0; w < 3; w++) slot[id].push_back(const_gemm(id, a, &l.weights[w * k * n], alen / k, k, n, false, &l.bias[w * n]));
+      continue;
+    }
+    if (l.kind == L_MATMUL2 || l.kind == L_CONCAT_MATMUL) {
+      o.kind = IO_GEMM2; o.in1 = tensor_of(e[1]);
+      const size_t blen = p.tensors[(size_t)o.in1].len;
+      if (l.kind == L_MATMUL2) {
+        DP_REQUIRE(l.nrows && alen % l.nrows == 0 && blen == l.nrows * l.ncols, DP_ERR_SHAPE, "matmul2: input shapes");
+        o.g.C = 1; o.g.R = alen / l.nrows; o.g.K = l.nrows; o.g.N = l.ncols; o.g.sAr = l.nrows; o.g.sAm = 1;
+        o.g.sBm = l.mm_transpose ? 1 : l.ncols; o.g.sBn = l.mm_transpose ? l.nrows : 1; o.g.sOr = l.ncols; o.g.sOn = 1;
+      } else {
+        DP_REQUIRE(alen == l.cm_a[0] * l.cm_a[1] * l.cm_a[2] && blen == l.cm_b[0] * l.cm_b[1] * l.cm_b[2], DP_ERR_SHAPE, "concat matmul: input shapes");
+        const CmShape g = cm_shape(l);
+        const size_t sa[3] = {l.cm_a[1] * l.cm_a[2], l.cm_a[2], 1}, sb[3] = {l.cm_b[1] * l.cm_b[2], l.cm_b[2], 1};
+        o.g.C = g.C; o.g.R = g.R; o.g.K = g.M; o.g.N = g.N;
+        o.g.sAc = sa[l.cm_left[0]]; o.g.sAm = sa[l.cm_left[1]]; o.g.sAr = sa[l.cm_left[2]];
+        o.g.sBc = sb[l.cm_right[0]]; o.g.sBm = sb[l.cm_right[1]]; o.g.sBn = sb[l.cm_right[2]];
+        // axis d of the permuted result is axis perm[d] of [C][R][N]
+        size_t so[3] = {g.R * g.N, g.N, 1};
+        if (!l.cm_perm.empty()) { const size_t st[3] = {g.out[1] * g.out[2], g.out[2], 1}; for (int d = 0; d < 3; d++) so[l.cm_perm[d]] = st[d]; }
+        o.g.sOc = so[0]; o.g.sOr = so[1]; o.g.sOn = so[2];
+      }
+      o.out = new_tensor(o.g.C * o.g.R * o.g.N, IQ_NO);
+      p.ops.push_back(o); slot[id] = {o.out};
+      continue;
+    }
+    if (l.kind == L_REQUANT) {
+      o.kind = IO_REQUANT; o.left = l.fixed_point_multiplier; o.shift = l.shift(); o.bits = l.intermediate_bit_size;
+      o.out = new_tensor(alen, IQ_YES);
+    } else if (l.kind == L_RELU) { o.kind = IO_RELU; o.out = new_tensor(alen, p.tensors[(size_t)a].q); }
+    else if (l.kind == L_ADD || l.kind == L_POSITIONAL) {
+      if (l.kind == L_ADD) DP_REQUIRE(alen == l.weights.size(), DP_ERR_SHAPE, "add: operand size mismatch");
+      else DP_REQUIRE(l.ncols && alen % l.ncols == 0 && alen <= l.weights.size(), DP_ERR_SHAPE, "positional: input shape");
+      o.kind = IO_ADDC; o.left = l.add_left; o.right = l.add_right; o.w = new_const(l.weights.data(), alen); o.out = new_tensor(alen, IQ_NO);
+    } else if (l.kind == L_ADD2) {
+      o.kind = IO_ADD2; o.in1 = tensor_of(e[1]); o.left = l.add_left; o.right = l.add_right;
+      DP_REQUIRE(alen == p.tensors[(size_t)o.in1].len, DP_ERR_SHAPE, "add2: inputs of different lengths");
+      o.out = new_tensor(alen, IQ_NO);
+    } else if (l.kind == L_EMBED) {
+      o.kind = IO_EMBED; o.w = new_const(l.weights.data(), l.nrows * l.ncols); o.d[0] = l.nrows; o.d[1] = l.ncols; o.out = new_tensor(alen * l.ncols, IQ_NO);
+    } else if (l.kind == L_MAXPOOL) {
+      DP_REQUIRE(alen == l.pin[0] * l.pin[1] * l.pin[2], DP_ERR_SHAPE, "maxpool: input size mismatch");
+      o.kind = IO_MAXPOOL; o.d[0] = l.pin[0]; o.d[1] = l.pin[1]; o.d[2] = l.pin[2]; o.out = new_tensor(alen / 4, p.tensors[(size_t)a].q);
+    } else if (l.kind == L_CONV) {
+      DP_REQUIRE(alen == l.kx * l.nw * l.nw, DP_ERR_SHAPE, "conv: input size mismatch");
+      o.kind = IO_CONV; o.w = new_const(l.weights.data(), l.weights.size()); o.bias = new_const(l.bias.data(), l.bias.size());
+      o.d[0] = l.kw; o.d[1] = l.kx; o.d[2] = l.real_nw; o.d[3] = l.nw; o.d[4] = l.unp_out[0]; o.d[5] = l.unp_out[1]; o.d[6] = l.unp_out[2];
+      o.out = new_tensor(l.kw * l.nw * l.nw, IQ_NO);
+    }
+    DP_REQUIRE(p.tensors[(size_t)o.out].len == lens[id], DP_ERR_SHAPE, "dp_model_infer: tensor length");
+    p.ops.push_back(o); slot[id] = {o.out};
+  }
+  for (const Edge& e : output_edges(m)) p.outputs.push_back(tensor_of(e));
+  return p;
+}
+#endif
+
+}  // namespace dp

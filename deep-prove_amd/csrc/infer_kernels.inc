@@ -1,0 +1,275 @@
+// Kernels and the batch runner of dp_model_infer (infer.h). Included by hip_dev.hip after HipDev; not part of kernels.inc (the SIMT-emulator
+// build of tests/ cuts its kernels from there). Activations are [batch][tensor] int64, with an int8 copy next to every tensor whose values are
+// known to lie within -128..127 (what a Requant writes, and what ReLU / MaxPool make of it): the int8 copies are the operands of k_infer_gemm_i8.
+// Bad data (a Requant input beyond its bit size, a token outside the vocabulary) raises bits of a device error word with a vector atomic; the
+// host reads it with the outputs. Every launch is finite; nothing here waits for the host.
+
+typedef int infer_v4i __attribute__((ext_vector_type(4)));
+typedef int infer_v16i __attribute__((ext_vector_type(16)));
+constexpr int IG_TM = 64, IG_TN = 64, IG_TK = 64, IG_LD = IG_TK + 16;  // tile of a workgroup (4 waves, 32 x 32 each); LDS row pitch in bytes
+constexpr unsigned INFER_ERR_REQUANT = 1, INFER_ERR_TOKEN = 2;
+
+// 16 consecutive int8 of row `row` of X[rows][K] from column k on, zeros outside the matrix. K % 16 == 0: one aligned 16-byte load
+__device__ __forceinline__ infer_v4i infer_ld16(const int8_t* __restrict__ X, size_t rows, size_t K, size_t row, size_t k, bool k16) {
+  infer_v4i v = {0, 0, 0, 0};
+  if (row >= rows || k >= K) return v;
+  if (k16) return *(const infer_v4i*)(X + row * K + k);
+  unsigned w[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < 16; j++) if (k + j < K) w[j >> 2] |= (unsigned)(uint8_t)X[row * K + k + j] << (8 * (j & 3));
+  v[0] = (int)w[0]; v[1] = (int)w[1]; v[2] = (int)w[2]; v[3] = (int)w[3];
+  return v;
+}
+// C[M][N] (int64) = A[M][K] (int8) * Bt[N][K]^T (int8) + bias[N], exact: v_mfma_i32_32x32x32_i8 accumulates in 32 bits and the caller has checked
+// K * 128 * 128 < 2^31. Operands are staged through LDS in K slices of 64; rows / columns / K beyond the matrices are zero-filled in registers
+// before they reach LDS, nothing is read past a buffer. Lane l of a wave holds 16 consecutive k (16 * (l >> 5) ...) of row l & 31 of A and of
+// column l & 31 of B: A and B fragments are cut from LDS by the SAME (lane half, byte) -> k rule, so the products pair up whatever order the
+// instruction gives the 32 k of a step. D: column = l & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (l >> 5).
+__global__ __launch_bounds__(256) void k_infer_gemm_i8(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, const int64_t* __restrict__ bias, int64_t* __restrict__ C, size_t M, size_t K, size_t N) {
+  __shared__ __attribute__((aligned(16))) int8_t As[IG_TM * IG_LD];
+  __shared__ __attribute__((aligned(16))) int8_t Bs[IG_TN * IG_LD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t m0 = (size_t)blockIdx.x * IG_TM, n0 = (size_t)blockIdx.y * IG_TN;
+  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
+  const int lr = tid >> 2, lc = (tid & 3) * 16;  // the 16 bytes of the slice this thread stages: tile row, byte column
+  const bool k16 = (K & 15) == 0;
+  infer_v16i acc;
+#pragma unroll
+  for (int r = 0; r < 16; r++) acc[r] = 0;
+  for (size_t k0 = 0; k0 < K; k0 += IG_TK) {
+    const infer_v4i a = infer_ld16(A, M, K, m0 + lr, k0 + lc, k16), b = infer_ld16(Bt, N, K, n0 + lr, k0 + lc, k16);
+    __syncthreads();  // (the fragments of the slice before have been read)
+    *(infer_v4i*)&As[lr * IG_LD + lc] = a;
+    *(infer_v4i*)&Bs[lr * IG_LD + lc] = b;
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < IG_TK / 32; s++) {
+      const infer_v4i fa = *(const infer_v4i*)&As[(wm + (lane & 31)) * IG_LD + s * 32 + (lane >> 5) * 16];
+      const infer_v4i fb = *(const infer_v4i*)&Bs[(wn + (lane & 31)) * IG_LD + s * 32 + (lane >> 5) * 16];
+      acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa, fb, acc, 0, 0, 0);
+    }
+  }
+  const size_t col = n0 + wn + (lane & 31);
+  if (col >= N) return;
+  const int64_t bv = bias ? bias[col] : 0;
+#pragma unroll
+  for (int r = 0; r < 16; r++) {
+    const size_t row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    if (row < M) C[row * N + col] = (int64_t)acc[r] + bv;
+  }
+}
+// the general product in 64-bit multiply-adds with the host's wrap-around (unsigned arithmetic): one output element per thread, n fastest.
+// B is a constant (lenB = 0) or a tensor of the batch
+__global__ __launch_bounds__(256) void k_infer_gemm_i64(const int64_t* __restrict__ A, size_t lenA, const int64_t* __restrict__ B, size_t lenB, const int64_t* __restrict__ bias,
+                                                        int64_t* __restrict__ O, size_t lenO, size_t batch, InferGemmShape g) {
+  const size_t per = g.C * g.R * g.N;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch * per) return;
+  const size_t b = i / per, e = i % per, n = e % g.N, r = (e / g.N) % g.R, c = e / (g.N * g.R);
+  const int64_t* a = A + b * lenA + c * g.sAc + r * g.sAr;
+  const int64_t* w = B + b * lenB + c * g.sBc + n * g.sBn;
+  uint64_t acc = 0;
+  for (size_t k = 0; k < g.K; k++) acc += (uint64_t)a[k * g.sAm] * (uint64_t)w[k * g.sBm];
+  if (bias) acc += (uint64_t)bias[n];
+  O[b * lenO + c * g.sOc + r * g.sOr + n * g.sOn] = (int64_t)acc;
+}
+// Requant::apply: (v * mult + 2^(sh-1)) >> sh clamped to +-127; |v| > 2^bits raises the error word (the host refuses the whole call, as run_model does)
+__global__ __launch_bounds__(256) void k_infer_requant(const int64_t* __restrict__ x, int64_t* __restrict__ o, int8_t* __restrict__ o8, size_t n, int64_t mult, unsigned sh, unsigned bits, unsigned* err) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t v = x[i];
+  const uint64_t mag = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
+  if (mag > (uint64_t(1) << bits)) atomicOr(err, INFER_ERR_REQUANT);
+  int64_t y = (int64_t)((uint64_t)v * (uint64_t)mult + (uint64_t(1) << (sh - 1))) >> sh;
+  y = y < -127 ? -127 : y > 127 ? 127 : y;
+  o[i] = y;
+  if (o8) o8[i] = (int8_t)y;
+}
+__global__ __launch_bounds__(256) void k_infer_relu(const int64_t* __restrict__ x, int64_t* __restrict__ o, int8_t* __restrict__ o8, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t v = x[i] < 0 ? 0 : x[i];
+  o[i] = v;
+  if (o8) o8[i] = (int8_t)v;
+}
+// Add with a static operand / Positional::Learned: left * x + right * w[i mod len] (w: the operand, or the first rows of the table)
+__global__ __launch_bounds__(256) void k_infer_addc(const int64_t* __restrict__ x, const int64_t* __restrict__ w, int64_t* __restrict__ o, size_t n, size_t len, int64_t left, int64_t right) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) o[i] = (int64_t)((uint64_t)left * (uint64_t)x[i] + (uint64_t)right * (uint64_t)w[i % len]);
+}
+__global__ __launch_bounds__(256) void k_infer_add2(const int64_t* __restrict__ x, const int64_t* __restrict__ y, int64_t* __restrict__ o, size_t n, int64_t left, int64_t right) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) o[i] = (int64_t)((uint64_t)left * (uint64_t)x[i] + (uint64_t)right * (uint64_t)y[i]);
+}
+// Embeddings: row tok[t] of the [vocab][emb] table for every token; a token outside the vocabulary raises the error word (and reads row 0)
+__global__ __launch_bounds__(256) void k_infer_embed(const int64_t* __restrict__ tok, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n, size_t vocab, size_t emb, unsigned* err) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int64_t t = tok[i / emb];
+  if (t < 0 || (uint64_t)t >= vocab) { atomicOr(err, INFER_ERR_TOKEN); t = 0; }
+  o[i] = table[(size_t)t * emb + i % emb];
+}
+// MaxPool 2 x 2, stride 2, on [batch][c][h][w]
+__global__ __launch_bounds__(256) void k_infer_maxpool(const int64_t* __restrict__ x, int64_t* __restrict__ o, int8_t* __restrict__ o8, size_t n, size_t h, size_t w) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t ow = w / 2, oh = h / 2, j = i % ow, r = (i / ow) % oh, plane = i / (ow * oh);  // plane = b * c + channel
+  const int64_t* p = x + plane * h * w + 2 * r * w + 2 * j;
+  const int64_t a = p[0] > p[1] ? p[0] : p[1], b = p[w] > p[w + 1] ? p[w] : p[w + 1], v = a > b ? a : b;
+  o[i] = v;
+  if (o8) o8[i] = (int8_t)v;
+}
+// Convolution::op on the padded tensors: the correlation the host's FFT product computes — on the FLAT index of a channel plane (offset a * nw + b,
+// terms that leave the plane dropped) —, + bias, then clear_garbage (zero outside the unpadded output shape). One output element per thread.
+__global__ __launch_bounds__(256) void k_infer_conv(const int64_t* __restrict__ x, const int64_t* __restrict__ f, const int64_t* __restrict__ bias, int64_t* __restrict__ o, size_t n,
+                                                    size_t kw, size_t kx, size_t rn, size_t nw, size_t u0, size_t u1, size_t u2) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t nn = nw * nw, p = i % nn, ch = (i / nn) % kw, b = i / (nn * kw), yy = p / nw, xx = p % nw;
+  if (!(ch < u0 && yy < u1 && xx < u2)) { o[i] = 0; return; }
+  uint64_t acc = (uint64_t)bias[ch];
+  for (size_t j = 0; j < kx; j++) {
+    const int64_t* xp = x + (b * kx + j) * nn;
+    const int64_t* fp = f + (ch * kx + j) * rn * rn;
+    for (size_t a = 0; a < rn; a++) for (size_t c = 0; c < rn; c++) { const size_t q = p + a * nw + c; if (q < nn) acc += (uint64_t)xp[q] * (uint64_t)fp[a * rn + c]; }
+  }
+  o[i] = (int64_t)acc;
+}
+// model input tensor `off .. off + len` of every sample, from the uploaded block (int8 when the host found every word within -128..127, else int64)
+__global__ __launch_bounds__(256) void k_infer_load(const int64_t* __restrict__ s64, const int8_t* __restrict__ s8, size_t stride, size_t off, size_t len, int64_t* __restrict__ o, int8_t* __restrict__ o8, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t src = (i / len) * stride + off + i % len;
+  const int64_t v = s8 ? (int64_t)s8[src] : s64[src];
+  o[i] = v;
+  if (o8) o8[i] = (int8_t)v;
+}
+__global__ __launch_bounds__(256) void k_infer_store(const int64_t* __restrict__ x, size_t len, int64_t* __restrict__ dst, size_t stride, size_t off, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[(i / len) * stride + off + i % len] = x[i];
+}
+
+struct InferDeviceState {
+  int device = 0;
+  std::vector<int64_t*> c64; std::vector<int8_t*> c8;
+  ~InferDeviceState() { (void)hipSetDevice(device); for (int64_t* p : c64) if (p) (void)hipFree(p); for (int8_t* p : c8) if (p) (void)hipFree(p); }
+};
+InferDeviceState* hip_infer_state_new(int device) { InferDeviceState* s = new InferDeviceState(); s->device = device; return s; }
+void hip_infer_state_free(InferDeviceState* s) { delete s; }
+
+void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* inputs, size_t ninputs, int64_t* outputs, size_t out_stride, double* wall_ms) {
+  HipDev* hd = static_cast<HipDev*>(d);
+  hd->bind_thread(); hd->sync();
+  hipStream_t s = hd->stream();
+  static const bool no_mfma = getenv("DP_INFER_NO_MFMA") && atoi(getenv("DP_INFER_NO_MFMA"));
+  static const bool log_line = getenv("DP_INFER_LOG") && atoi(getenv("DP_INFER_LOG"));
+  const char* mbs = getenv("DP_INFER_SCRATCH_MB");
+  const size_t scratch_cap = (mbs && atoll(mbs) > 0 ? (size_t)atoll(mbs) : size_t(1024)) << 20;
+  const auto t0 = std::chrono::steady_clock::now();
+  // model inputs within -128..127 (checked here, on the host, for the whole call): they travel as int8 and count as quantised tensors
+  bool in_q = true;
+  for (size_t i = 0, n = ninputs * p.input_len; i < n && in_q; i++) in_q = inputs[i] >= -128 && inputs[i] <= 127;
+  const size_t nt = p.tensors.size();
+  std::vector<char> q(nt);
+  size_t per_sample = 0;
+  auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+  for (size_t t = 0; t < nt; t++) { q[t] = p.tensors[t].q == IQ_YES || (p.tensors[t].q == IQ_IF_INPUTS && in_q); per_sample += p.tensors[t].len * (q[t] ? 9 : 8); }
+  per_sample += p.input_len * (in_q ? 1 : 8) + p.output_len * 8;
+  size_t chunk = std::max<size_t>(1, std::min(ninputs, scratch_cap / std::max<size_t>(per_sample, 1)));
+  // constants: on the device from the first launch that reads them on (freed with the model)
+  st->c64.resize(p.consts.size(), nullptr); st->c8.resize(p.consts.size(), nullptr);
+  auto const64 = [&](int c) -> const int64_t* {
+    if (c < 0) return nullptr;
+    if (!st->c64[(size_t)c]) { int64_t* dp_ = nullptr; HIP_CHECK(hipMalloc((void**)&dp_, std::max<size_t>(p.consts[(size_t)c].n, 1) * 8)); st->c64[(size_t)c] = dp_; HIP_CHECK(hipMemcpy(dp_, p.consts[(size_t)c].h64, p.consts[(size_t)c].n * 8, hipMemcpyHostToDevice)); }
+    return st->c64[(size_t)c];
+  };
+  auto const8 = [&](int c) -> const int8_t* {
+    if (!st->c8[(size_t)c]) { int8_t* dp_ = nullptr; HIP_CHECK(hipMalloc((void**)&dp_, p.consts[(size_t)c].w8.size())); st->c8[(size_t)c] = dp_; HIP_CHECK(hipMemcpy(dp_, p.consts[(size_t)c].w8.data(), p.consts[(size_t)c].w8.size(), hipMemcpyHostToDevice)); }
+    return st->c8[(size_t)c];
+  };
+  // scratch of one chunk (outside the arenas, released before the call returns): [tensors, int64 | int8][input block][output block][error word]
+  std::vector<size_t> off64(nt), off8(nt);
+  size_t total = 0;
+  for (size_t t = 0; t < nt; t++) { off64[t] = total; total += up(chunk * p.tensors[t].len * 8); off8[t] = total; if (q[t]) total += up(chunk * p.tensors[t].len); }
+  const size_t in_bytes = chunk * p.input_len * (in_q ? 1 : 8), out_words = chunk * p.output_len + 1;
+  const size_t off_in = total; total += up(in_bytes);
+  const size_t off_out = total; total += up(out_words * 8);
+  char* scratch = nullptr; char* pinned = nullptr;
+  size_t launches[IO_KINDS + 2] = {0}, n_i8 = 0, n_i64 = 0, nchunks = 0;
+  unsigned err = 0;
+  auto cleanup = [&] { (void)hipStreamSynchronize(s); if (scratch) (void)hipFree(scratch); if (pinned) (void)hipHostFree(pinned); scratch = pinned = nullptr; };
+  try {
+    HIP_CHECK(hipMalloc((void**)&scratch, total));
+    HIP_CHECK(hipHostMalloc((void**)&pinned, std::max(in_bytes, out_words * 8), hipHostMallocDefault));
+    auto T64 = [&](int t) { return (int64_t*)(scratch + off64[(size_t)t]); };
+    auto T8 = [&](int t) { return q[(size_t)t] ? (int8_t*)(scratch + off8[(size_t)t]) : (int8_t*)nullptr; };
+    int64_t* dout = (int64_t*)(scratch + off_out);
+    unsigned* derr = (unsigned*)(dout + chunk * p.output_len);
+    auto grid = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    for (size_t b0 = 0; b0 < ninputs && !err; b0 += chunk, nchunks++) {
+      const size_t nb = std::min(chunk, ninputs - b0), nin = nb * p.input_len;
+      if (in_q) { int8_t* h = (int8_t*)pinned; const int64_t* src = inputs + b0 * p.input_len; for (size_t i = 0; i < nin; i++) h[i] = (int8_t)src[i]; }
+      else memcpy(pinned, inputs + b0 * p.input_len, nin * 8);
+      HIP_CHECK(hipMemcpyAsync(scratch + off_in, pinned, nin * (in_q ? 1 : 8), hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemsetAsync(derr, 0, 8, s));
+      size_t ioff = 0;
+      for (int t : p.inputs) {
+        const size_t len = p.tensors[(size_t)t].len, n = nb * len;
+        k_infer_load<<<grid(n), 256, 0, s>>>(in_q ? nullptr : (const int64_t*)(scratch + off_in), in_q ? (const int8_t*)(scratch + off_in) : nullptr, p.input_len, ioff, len, T64(t), T8(t), n);
+        ioff += len; launches[IO_KINDS]++;
+      }
+      for (const InferOp& o : p.ops) {
+        const size_t n = nb * p.tensors[(size_t)o.out].len;
+        launches[o.kind]++;
+        switch (o.kind) {
+          case IO_GEMM: {
+            const bool i8 = !no_mfma && q[(size_t)o.in0] && !p.consts[(size_t)o.w].w8.empty();
+            if (i8) {
+              const size_t M = nb * o.g.R;
+              k_infer_gemm_i8<<<dim3((unsigned)((M + IG_TM - 1) / IG_TM), (unsigned)((o.g.N + IG_TN - 1) / IG_TN)), 256, 0, s>>>(T8(o.in0), const8(o.w), const64(o.bias), T64(o.out), M, o.g.K, o.g.N);
+              n_i8++;
+            } else {
+              k_infer_gemm_i64<<<grid(n), 256, 0, s>>>(T64(o.in0), p.tensors[(size_t)o.in0].len, const64(o.w), 0, const64(o.bias), T64(o.out), p.tensors[(size_t)o.out].len, nb, o.g);
+              n_i64++;
+            }
+            break;
+          }
+          case IO_GEMM2:
+            k_infer_gemm_i64<<<grid(n), 256, 0, s>>>(T64(o.in0), p.tensors[(size_t)o.in0].len, T64(o.in1), p.tensors[(size_t)o.in1].len, nullptr, T64(o.out), p.tensors[(size_t)o.out].len, nb, o.g);
+            n_i64++;
+            break;
+          case IO_REQUANT: k_infer_requant<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.out), T8(o.out), n, o.left, o.shift, o.bits, derr); break;
+          case IO_RELU: k_infer_relu<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.out), T8(o.out), n); break;
+          case IO_ADDC: k_infer_addc<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.w), T64(o.out), n, p.tensors[(size_t)o.out].len, o.left, o.right); break;
+          case IO_ADD2: k_infer_add2<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.in1), T64(o.out), n, o.left, o.right); break;
+          case IO_EMBED: k_infer_embed<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.w), T64(o.out), n, o.d[0], o.d[1], derr); break;
+          case IO_MAXPOOL: k_infer_maxpool<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.out), T8(o.out), n, o.d[1], o.d[2]); break;
+          case IO_CONV: k_infer_conv<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.w), const64(o.bias), T64(o.out), n, o.d[0], o.d[1], o.d[2], o.d[3], o.d[4], o.d[5], o.d[6]); break;
+          default: throw DpError(DP_ERR_ARG, "dp_model_infer: unknown op");
+        }
+      }
+      size_t ooff = 0;
+      for (int t : p.outputs) {
+        const size_t len = p.tensors[(size_t)t].len, n = nb * len;
+        k_infer_store<<<grid(n), 256, 0, s>>>(T64(t), len, dout, p.output_len, ooff, n);
+        ooff += len; launches[IO_KINDS + 1]++;
+      }
+      HIP_CHECK(hipGetLastError());
+      // the outputs and the error word behind them: one copy (a partial last chunk: the word is fetched on its own)
+      const size_t nout = nb * p.output_len;
+      if (nb == chunk) HIP_CHECK(hipMemcpyAsync(pinned, dout, (nout + 1) * 8, hipMemcpyDeviceToHost, s));
+      else { HIP_CHECK(hipMemcpyAsync(pinned, dout, nout * 8, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipMemcpyAsync(pinned + nout * 8, derr, 8, hipMemcpyDeviceToHost, s)); }
+      HIP_CHECK(hipStreamSynchronize(s));
+      err = *(const unsigned*)(pinned + nout * 8);
+      if (!err) for (size_t i = 0; i < nb; i++) memcpy(outputs + (b0 + i) * out_stride, pinned + i * p.output_len * 8, p.output_len * 8);
+    }
+  } catch (...) { cleanup(); throw; }
+  cleanup();
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (wall_ms) *wall_ms = ms;
+  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu conv %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms\n",
+                   n_i8, n_i64, launches[IO_CONV], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1],
+                   ninputs, nchunks, chunk, (double)total / 1048576.0, in_q ? "int8" : "int64", ms);
+  DP_REQUIRE(!(err & INFER_ERR_REQUANT), DP_ERR_ARG, "requant: value exceeds intermediate bit size");
+  DP_REQUIRE(!(err & INFER_ERR_TOKEN), DP_ERR_ARG, "embeddings: token outside the vocabulary");
+}

@@ -1,0 +1,44 @@
+"""Batched quantised inference on the device: ctypes binding of include/deep_prove_hip_infer.h (dp_model_infer). The entry point has a header and a
+binding table of its own: `_lib.SIGNATURES` lists exactly the symbols of include/deep_prove_hip.h."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, i64p, vp
+
+# name -> (restype, argtypes): every symbol declared in include/deep_prove_hip_infer.h
+INFER_SIGNATURES = {
+    "dp_model_infer": (C.c_int32, [vp, i64p, C.c_size_t, C.c_size_t, i64p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_double)]),
+}
+
+_bound = None
+
+
+def _load():
+    global _bound
+    if _bound is None:
+        lib = _lib.load()
+        for name, (res, args) in INFER_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _bound = lib
+    return _bound
+
+
+def infer(ctx, inputs_i64):
+    """Model::run for every row of inputs_i64[n, ninput] on the context's GPU; returns (outputs[n, nout], wall_ms). The integers are those of
+    infer_host, row by row. Models with LayerNorm / Softmax / Mha / GELU nodes raise DeepProveError (DP_ERR_ARG)."""
+    lib = _load()
+    x = np.ascontiguousarray(inputs_i64, dtype=np.int64)
+    if x.ndim == 1:
+        x = x.reshape(1, -1)
+    n, ninput = x.shape
+    cap = C.c_size_t(0)
+    check(lib.dp_model_output_len(ctx.h, C.byref(cap)))
+    outs = np.empty((n, cap.value), dtype=np.int64)
+    no = C.c_size_t(0)
+    ms = C.c_double()
+    check(lib.dp_model_infer(ctx.h, x.ctypes.data_as(i64p), n, ninput, outs.ctypes.data_as(i64p), cap.value, C.byref(no), C.byref(ms)))
+    return outs[:, :no.value].copy(), ms.value

@@ -130,3 +130,7 @@ impl Drop for Words { fn drop(&mut self) { if !self.ptr.is_null() { unsafe { dp_
 // the buffer is plain memory owned by this value; the library's allocator is thread safe (csrc/capi.cpp, OutPool)
 unsafe impl Send for Words {}
 unsafe impl Sync for Words {}
+
+/// `include/deep_prove_hip_infer.h`: batched quantised inference on the device (`dp_model_infer`), declared in a module of its own.
+pub mod infer;
+pub use infer::dp_model_infer;
