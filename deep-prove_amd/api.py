@@ -564,10 +564,11 @@ class Context:
         check(_lib.load().dp_model_verifier_blob(self.h, C.byref(pw), C.byref(pn)))
         return _take(pw, pn.value)
 
-    def infer(self, inputs_i64):
-        """dp_model_infer: Model::run for every row of inputs_i64[n, ninput] on this context's GPU; returns (outputs[n, nout], wall_ms)"""
+    def infer(self, inputs_i64, all_kinds=False):
+        """dp_model_infer: Model::run for every row of inputs_i64[n, ninput] on this context's GPU; returns (outputs[n, nout], wall_ms).
+        all_kinds (dp_model_infer_ex, DP_INFER_ALL_KINDS): also models with LayerNorm / Softmax / Mha / GELU nodes"""
         from .infer import infer
-        return infer(self, inputs_i64)
+        return infer(self, inputs_i64, all_kinds=all_kinds)
 
     def free(self):
         if self.h:

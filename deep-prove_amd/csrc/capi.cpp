@@ -52,8 +52,9 @@ struct dp_model {
   dp_ctx* ctx; std::unique_ptr<Context> zk; std::vector<std::unique_ptr<Dev>> workers; std::vector<dp::Cohort*> cohorts;
   size_t last_in_flight = 0, in_flight_cap = 0; size_t prove_peak = 0;  // largest arena footprint a proof of this model has had so far (sizes the arenas of batch workers)
   // dp_model_infer: the flattened model and its constants on the device, made at the first call (dp_model_setup allocates nothing for them)
-  std::unique_ptr<InferProgram> infer_prog; InferDeviceState* infer_state = nullptr;
-  ~dp_model() { for (size_t i = cohorts.size(); i-- > 0;) hip_cohort_free(cohorts[i]); if (infer_state) hip_infer_state_free(infer_state); }  // (last first: a cohort that shares a stream goes before the one that owns it)
+  // ([flags]: a program per flag word of dp_model_infer_ex, each with its constants)
+  std::unique_ptr<InferProgram> infer_prog[2]; InferDeviceState* infer_state[2] = {nullptr, nullptr};
+  ~dp_model() { for (size_t i = cohorts.size(); i-- > 0;) hip_cohort_free(cohorts[i]); for (InferDeviceState* st : infer_state) if (st) hip_infer_state_free(st); }  // (last first: a cohort that shares a stream goes before the one that owns it)
 };
 
 // Every cohort stream needs a hardware queue of its own (24 are served without time slicing; the HIP runtime multiplexes streams
@@ -1370,18 +1371,23 @@ int32_t dp_model_infer_host(const int64_t* model_blob, size_t nwords, const int6
   });
 }
 int32_t dp_model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms) {
+  return dp_model_infer_ex(m, inputs, ninputs, ninput, 0, outputs, noutput_cap, noutput, wall_ms);
+}
+int32_t dp_model_infer_ex(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms) {
   return guard([&] {
     DP_REQUIRE(m && inputs && outputs && noutput, DP_ERR_ARG, "bad arguments");
+    DP_REQUIRE(!(flags & ~(uint32_t)DP_INFER_ALL_KINDS), DP_ERR_ARG, "dp_model_infer_ex: unknown flag bits");
     const ModelSpec& spec = m->zk->model;
     DP_REQUIRE(ninput == spec.input_len, DP_ERR_SHAPE, "input length mismatch");
     CtxLock lk(m->ctx);
-    if (!m->infer_prog) m->infer_prog.reset(new InferProgram(infer_plan(spec)));  // (refuses LayerNorm / Softmax / Mha / GELU before any device work)
-    DP_REQUIRE(noutput_cap >= m->infer_prog->output_len, DP_ERR_ARG, "output buffer too small");
-    *noutput = m->infer_prog->output_len;
+    std::unique_ptr<InferProgram>& prog = m->infer_prog[flags];
+    if (!prog) prog.reset(new InferProgram(infer_plan(spec, flags)));  // (flags 0: refuses LayerNorm / Softmax / Mha / GELU before any device work)
+    DP_REQUIRE(noutput_cap >= prog->output_len, DP_ERR_ARG, "output buffer too small");
+    *noutput = prog->output_len;
     if (wall_ms) *wall_ms = 0;
     if (!ninputs) return;
-    if (!m->infer_state) m->infer_state = hip_infer_state_new(m->ctx->device_id);
-    hip_infer_run(m->ctx->dev, *m->infer_prog, m->infer_state, inputs, ninputs, outputs, noutput_cap, wall_ms);
+    if (!m->infer_state[flags]) m->infer_state[flags] = hip_infer_state_new(m->ctx->device_id);
+    hip_infer_run(m->ctx->dev, *prog, m->infer_state[flags], inputs, ninputs, outputs, noutput_cap, wall_ms);
   });
 }
 int32_t dp_host_poseidon2(uint64_t state[8], int32_t force_scalar, int32_t* vectorised) {

@@ -4,9 +4,20 @@
 // Which products take the i8 MFMA is decided here, statically: the weights within -128..127, K * 128 * 128 < 2^31 and the input produced by
 // a Requant (through ReLU / MaxPool / Flatten) or a model input the host has range-checked at upload. Everything else is 64-bit multiply-add
 // with the host's wrap-around.
+// INFER_ALL_KINDS (dp_model_infer_ex, DP_INFER_ALL_KINDS) adds LayerNorm, Softmax, Mha and GELU. Their tables are constants of the model, made
+// here by the functions the prover uses (gelu_lut, inv_sqrt_lut, softmax_lut); on the device the three layers are integer work. The one float
+// computation that depends on the data, the shift of a Softmax row, stays on the host: at an IO_SOFTMAX hip_infer_run downloads the input of
+// the chunk, calls InferProgram::shifts (infer_softmax_shifts below: softmax_row_shift of zkml.h, the function softmax_op calls) and uploads
+// one shift per row. An Mha node is three ops: the product Q K^T, the Softmax, the product with V.
 #pragma once
 #include "dev.h"
+#include <algorithm>
+#include <atomic>
 #include <cstdint>
+#include <cstdlib>
+#include <functional>
+#include <map>
+#include <thread>
 #include <vector>
 
 namespace dp {
@@ -15,18 +26,26 @@ enum InferQ { IQ_NO = 0, IQ_YES = 1, IQ_IF_INPUTS = 2 };  // every value of the 
 struct InferTensor { size_t len = 0; int q = IQ_NO; };
 // a constant of the model. h64 points into the ModelSpec (it lives as long as the dp_model); w8 = the same matrix as int8, transposed to [N][K]
 // (both operands of k_infer_gemm_i8 are read along K), empty when a weight does not fit. Uploaded at the first launch that reads it.
-struct InferConst { const int64_t* h64 = nullptr; size_t n = 0; std::vector<int8_t> w8; };
-enum InferOpKind { IO_GEMM = 0, IO_GEMM2, IO_REQUANT, IO_RELU, IO_ADDC, IO_ADD2, IO_EMBED, IO_MAXPOOL, IO_CONV, IO_KINDS };
+// A table (GELU, inverse square root, exponential) is made by the planner and lives in `own`.
+struct InferConst {
+  const int64_t* h64 = nullptr; size_t n = 0; std::vector<int8_t> w8; std::vector<int64_t> own;
+  const int64_t* data() const { return own.empty() ? h64 : own.data(); }
+};
+constexpr uint32_t INFER_ALL_KINDS = 1;  // (DP_INFER_ALL_KINDS of the public header)
+enum InferOpKind { IO_GEMM = 0, IO_GEMM2, IO_REQUANT, IO_RELU, IO_ADDC, IO_ADD2, IO_EMBED, IO_MAXPOOL, IO_CONV, IO_GELU, IO_LAYERNORM, IO_SOFTMAX, IO_KINDS };
 // out[b][c*sOc + r*sOr + n*sOn] = sum_m A[b][c*sAc + r*sAr + m*sAm] * B[(B a tensor: b)][c*sBc + m*sBm + n*sBn] (+ bias[n])
 struct InferGemmShape { size_t C = 1, R = 0, K = 0, N = 0; size_t sAc = 0, sAr = 0, sAm = 0, sBc = 0, sBm = 0, sBn = 0, sOc = 0, sOr = 0, sOn = 0; };
 struct InferOp {
   int kind = IO_GEMM, node = 0;
   int in0 = -1, in1 = -1, out = -1;  // tensors
-  int w = -1, bias = -1;             // constants
+  int w = -1, bias = -1;             // constants (IO_LAYERNORM: gamma, beta)
+  int table = -1;                    // constant: the table of IO_GELU (rows -max .. max - 1), IO_LAYERNORM (rows -2^14 .. 2^14 - 1), IO_SOFTMAX (2^table bits rows)
   InferGemmShape g;                  // IO_GEMM (B = constant w; the i8 form when in0 is q and w has an int8 copy), IO_GEMM2 (B = tensor in1)
-  int64_t left = 1, right = 1;       // IO_ADDC: left * x + right * w[i]; IO_ADD2: left * a + right * b; IO_REQUANT: left = multiplier
-  unsigned shift = 0, bits = 0;      // IO_REQUANT
-  size_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // IO_EMBED: vocabulary, embedding size; IO_MAXPOOL: c, h, w; IO_CONV: kw, kx, real_nw, nw, unp_out[3]
+  int64_t left = 1, right = 1;       // IO_ADDC: left * x + right * w[i]; IO_ADD2: left * a + right * b; IO_REQUANT, IO_GELU, IO_LAYERNORM: left = multiplier; IO_SOFTMAX: left = scalar, right = bkm
+  unsigned shift = 0, bits = 0;      // IO_REQUANT; IO_LAYERNORM: shift = range_check_bits; IO_SOFTMAX: bits = table bits
+  // IO_EMBED: vocabulary, embedding size; IO_MAXPOOL: c, h, w; IO_CONV: kw, kx, real_nw, nw, unp_out[3]; IO_GELU: max; IO_LAYERNORM: row length, N;
+  // IO_SOFTMAX: C, R, K, zero chunks, zero vars (in1 = the shift buffer of the chunk, a tensor of C * R words per sample)
+  size_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 struct InferProgram {
   size_t input_len = 0, output_len = 0;
@@ -34,6 +53,8 @@ struct InferProgram {
   std::vector<int> inputs, outputs;  // tensor ids of the model's input / output tensors, in the order they are concatenated
   std::vector<InferConst> consts;
   std::vector<InferOp> ops;
+  // the shift step of an IO_SOFTMAX: x = its input for nb samples; shifts: nb x C * R words. False: an input beyond 2^24 (no shift is made of such a sample)
+  std::function<bool(const InferOp& o, const int64_t* x, size_t nb, int64_t* shifts)> shifts;
 };
 struct InferDeviceState;  // the constants on the device (made at the first call, freed with the model)
 InferDeviceState* hip_infer_state_new(int device);
@@ -46,9 +67,33 @@ inline const char* infer_kind_name(int k) {
   static const char* names[] = {"Dense", "Requant", "ReLU", "Conv", "MaxPool", "Flatten", "MatMul", "Add", "Embeddings", "Positional", "MatMul2", "Add2", "ConcatMatMul", "QKV", "LayerNorm", "Softmax", "Mha", "GELU"};
   return k >= 0 && k < 18 ? names[k] : "unknown";
 }
-inline InferProgram infer_plan(const ModelSpec& m) {
+// the shifts of every Softmax row of nb samples over at most DP_HOST_THREADS threads (never more than 16); every row is range checked before
+// softmax_row_shift sees it, as softmax_op does
+inline bool infer_softmax_shifts(const LayerSpec& sm, const int64_t* x, size_t nb, int64_t* shifts) {
+  const size_t C = sm.sm_shape[0], R = sm.sm_shape[1], K = sm.sm_shape[2], rows = nb * C * R;
+  const char* te = getenv("DP_HOST_THREADS");
+  size_t nth = te ? (size_t)std::max(1, atoi(te)) : (size_t)std::max(1.0, host_cpu_budget() - 2.0);
+  nth = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(nth, 16), rows / 256));
+  std::atomic<bool> ok(true);
+  auto part = [&](size_t t) {
+    for (size_t i = rows * t / nth, e = rows * (t + 1) / nth; i < e && ok.load(std::memory_order_relaxed); i++) {
+      const int64_t* row = x + i * K;
+      bool in = true;
+      for (size_t j = 0; j < K; j++) in = in && row[j] >= -(int64_t(1) << 24) && row[j] <= (int64_t(1) << 24);
+      if (!in) { ok = false; return; }
+      shifts[i] = softmax_row_shift(sm, row, i % R + 1);
+    }
+  };
+  std::vector<std::thread> th;
+  for (size_t t = 1; t < nth; t++) th.emplace_back(part, t);
+  part(0);
+  for (std::thread& t : th) t.join();
+  return ok;
+}
+inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
   for (size_t id = 0; id < m.layers.size(); id++) {
     const int k = m.layers[id].kind;
+    if ((flags & INFER_ALL_KINDS) && k >= L_LAYERNORM && k <= L_GELU) continue;
     DP_REQUIRE(k >= L_DENSE && k <= L_QKV, DP_ERR_ARG, "dp_model_infer: node " + std::to_string(id) + " is a " + infer_kind_name(k) + " layer (kind " + std::to_string(k) +
                "): LayerNorm, Softmax, Mha and GELU are not inferred on the device yet");
   }
@@ -79,6 +124,47 @@ inline InferProgram infer_plan(const ModelSpec& m) {
     p.ops.push_back(o);
     return o.out;
   };
+  // a table of the model: the output column, made once per (kind, parameters)
+  std::map<TableType, int> tables;
+  auto table_const = [&](const TableType& tt) {
+    auto it = tables.find(tt);
+    if (it != tables.end()) return it->second;
+    InferConst c;
+    if (tt.kind == 1) { const int64_t mx = int64_t(1) << (tt.size - 1); for (int64_t i = -mx; i < mx; i++) c.own.push_back(gelu_lut(i)); }
+    else if (tt.kind == 7) { const int64_t mx = int64_t(1) << (2 * (Q_BIT_LEN - 1)); for (int64_t i = -mx; i < mx; i++) c.own.push_back(inv_sqrt_lut(tt.aux, tt.size, i)); }
+    else for (int64_t j = 0; j < (int64_t(1) << tt.size); j++) c.own.push_back(softmax_lut(tt.aux, tt.aux2, j));
+    c.n = c.own.size();
+    p.consts.push_back(std::move(c));
+    return tables[tt] = (int)p.consts.size() - 1;
+  };
+  // the product of two tensors a ConcatMatMul describes (also the two products of an Mha node)
+  auto cm_gemm = [&](size_t id, const LayerSpec& l, int a, int b) {
+    InferOp o; o.kind = IO_GEMM2; o.node = (int)id; o.in0 = a; o.in1 = b;
+    DP_REQUIRE(p.tensors[(size_t)a].len == l.cm_a[0] * l.cm_a[1] * l.cm_a[2] && p.tensors[(size_t)b].len == l.cm_b[0] * l.cm_b[1] * l.cm_b[2], DP_ERR_SHAPE, "concat matmul: input shapes");
+    const CmShape g = cm_shape(l);
+    const size_t sa[3] = {l.cm_a[1] * l.cm_a[2], l.cm_a[2], 1}, sb[3] = {l.cm_b[1] * l.cm_b[2], l.cm_b[2], 1};
+    o.g.C = g.C; o.g.R = g.R; o.g.K = g.M; o.g.N = g.N;
+    o.g.sAc = sa[l.cm_left[0]]; o.g.sAm = sa[l.cm_left[1]]; o.g.sAr = sa[l.cm_left[2]];
+    o.g.sBc = sb[l.cm_right[0]]; o.g.sBm = sb[l.cm_right[1]]; o.g.sBn = sb[l.cm_right[2]];
+    // axis d of the permuted result is axis perm[d] of [C][R][N]
+    size_t so[3] = {g.R * g.N, g.N, 1};
+    if (!l.cm_perm.empty()) { const size_t st[3] = {g.out[1] * g.out[2], g.out[2], 1}; for (int d = 0; d < 3; d++) so[l.cm_perm[d]] = st[d]; }
+    o.g.sOc = so[0]; o.g.sOr = so[1]; o.g.sOn = so[2];
+    o.out = new_tensor(o.g.C * o.g.R * o.g.N, IQ_NO);
+    p.ops.push_back(o);
+    return o.out;
+  };
+  auto softmax = [&](size_t id, const LayerSpec& l, int a) {
+    const size_t C = l.sm_shape[0], R = l.sm_shape[1], K = l.sm_shape[2];
+    DP_REQUIRE(C && R && R == K && p.tensors[(size_t)a].len == C * R * K, DP_ERR_SHAPE, "softmax: shapes");
+    DP_REQUIRE(l.sm_table_size <= 24 && 16 + l.sm_table_size + l.sm_zero_chunks * l.sm_zero_vars <= 63, DP_ERR_ARG, "softmax: table sizes");
+    InferOp o; o.kind = IO_SOFTMAX; o.node = (int)id; o.in0 = a; o.in1 = new_tensor(C * R, IQ_NO);
+    o.table = table_const(softmax_table(l)); o.left = l.sm_scalar; o.right = l.sm_bkm; o.bits = l.sm_table_size;
+    o.d[0] = C; o.d[1] = R; o.d[2] = K; o.d[3] = l.sm_zero_chunks; o.d[4] = l.sm_zero_vars;
+    o.out = new_tensor(C * R * K, IQ_NO);
+    p.ops.push_back(o);
+    return o.out;
+  };
   for (size_t id = 0; id < m.layers.size(); id++) {
     const LayerSpec& l = m.layers[id];
     const std::vector<Edge> e = edges_in(m, id);
@@ -99,25 +185,22 @@ inline InferProgram infer_plan(const ModelSpec& m) {
       for (size_t w = 0; w < 3; w++) slot[id].push_back(const_gemm(id, a, &l.weights[w * k * n], alen / k, k, n, false, &l.bias[w * n]));
       continue;
     }
-    if (l.kind == L_MATMUL2 || l.kind == L_CONCAT_MATMUL) {
+    if (l.kind == L_CONCAT_MATMUL) { slot[id] = {cm_gemm(id, l, a, tensor_of(e[1]))}; continue; }
+    if (l.kind == L_MHA) {  // qk on (Q, K), the Softmax straight on the products, final_mul on (probabilities, V)
+      const size_t n = l.mha_shape[0] * l.mha_shape[1] * l.mha_shape[2];
+      const int kt = tensor_of(e[1]), vt = tensor_of(e[2]);
+      DP_REQUIRE(alen == n && p.tensors[(size_t)kt].len == n && p.tensors[(size_t)vt].len == n, DP_ERR_SHAPE, "mha: input shapes");
+      slot[id] = {cm_gemm(id, mha_final_spec(l), softmax(id, mha_softmax_spec(l), cm_gemm(id, mha_qk_spec(l), a, kt)), vt)};
+      DP_REQUIRE(p.tensors[(size_t)slot[id][0]].len == lens[id], DP_ERR_SHAPE, "dp_model_infer: tensor length");
+      continue;
+    }
+    if (l.kind == L_SOFTMAX) { slot[id] = {softmax(id, l, a)}; continue; }
+    if (l.kind == L_MATMUL2) {
       o.kind = IO_GEMM2; o.in1 = tensor_of(e[1]);
       const size_t blen = p.tensors[(size_t)o.in1].len;
-      if (l.kind == L_MATMUL2) {
-        DP_REQUIRE(l.nrows && alen % l.nrows == 0 && blen == l.nrows * l.ncols, DP_ERR_SHAPE, "matmul2: input shapes");
-        o.g.C = 1; o.g.R = alen / l.nrows; o.g.K = l.nrows; o.g.N = l.ncols; o.g.sAr = l.nrows; o.g.sAm = 1;
-        o.g.sBm = l.mm_transpose ? 1 : l.ncols; o.g.sBn = l.mm_transpose ? l.nrows : 1; o.g.sOr = l.ncols; o.g.sOn = 1;
-      } else {
-        DP_REQUIRE(alen == l.cm_a[0] * l.cm_a[1] * l.cm_a[2] && blen == l.cm_b[0] * l.cm_b[1] * l.cm_b[2], DP_ERR_SHAPE, "concat matmul: input shapes");
-        const CmShape g = cm_shape(l);
-        const size_t sa[3] = {l.cm_a[1] * l.cm_a[2], l.cm_a[2], 1}, sb[3] = {l.cm_b[1] * l.cm_b[2], l.cm_b[2], 1};
-        o.g.C = g.C; o.g.R = g.R; o.g.K = g.M; o.g.N = g.N;
-        o.g.sAc = sa[l.cm_left[0]]; o.g.sAm = sa[l.cm_left[1]]; o.g.sAr = sa[l.cm_left[2]];
-        o.g.sBc = sb[l.cm_right[0]]; o.g.sBm = sb[l.cm_right[1]]; o.g.sBn = sb[l.cm_right[2]];
-        // axis d of the permuted result is axis perm[d] of [C][R][N]
-        size_t so[3] = {g.R * g.N, g.N, 1};
-        if (!l.cm_perm.empty()) { const size_t st[3] = {g.out[1] * g.out[2], g.out[2], 1}; for (int d = 0; d < 3; d++) so[l.cm_perm[d]] = st[d]; }
-        o.g.sOc = so[0]; o.g.sOr = so[1]; o.g.sOn = so[2];
-      }
+      DP_REQUIRE(l.nrows && alen % l.nrows == 0 && blen == l.nrows * l.ncols, DP_ERR_SHAPE, "matmul2: input shapes");
+      o.g.C = 1; o.g.R = alen / l.nrows; o.g.K = l.nrows; o.g.N = l.ncols; o.g.sAr = l.nrows; o.g.sAm = 1;
+      o.g.sBm = l.mm_transpose ? 1 : l.ncols; o.g.sBn = l.mm_transpose ? l.nrows : 1; o.g.sOr = l.ncols; o.g.sOn = 1;
       o.out = new_tensor(o.g.C * o.g.R * o.g.N, IQ_NO);
       p.ops.push_back(o); slot[id] = {o.out};
       continue;
@@ -144,11 +227,24 @@ inline InferProgram infer_plan(const ModelSpec& m) {
       o.kind = IO_CONV; o.w = new_const(l.weights.data(), l.weights.size()); o.bias = new_const(l.bias.data(), l.bias.size());
       o.d[0] = l.kw; o.d[1] = l.kx; o.d[2] = l.real_nw; o.d[3] = l.nw; o.d[4] = l.unp_out[0]; o.d[5] = l.unp_out[1]; o.d[6] = l.unp_out[2];
       o.out = new_tensor(l.kw * l.nw * l.nw, IQ_NO);
+    } else if (l.kind == L_GELU) {
+      const TableType tt = gelu_table(l);
+      o.kind = IO_GELU; o.table = table_const(tt); o.left = l.fixed_point_multiplier; o.d[0] = size_t(1) << (tt.size - 1); o.out = new_tensor(alen, IQ_NO);
+    } else if (l.kind == L_LAYERNORM) {
+      const size_t fd = l.weights.size();
+      DP_REQUIRE((fd && !(fd & (fd - 1))) && l.bias.size() == fd && alen % fd == 0 && l.ln_dim_size >= 1 && l.ln_dim_size <= fd && l.ln_range_check_bits < 64, DP_ERR_SHAPE, "layernorm: shapes");
+      o.kind = IO_LAYERNORM; o.w = new_const(l.weights.data(), fd); o.bias = new_const(l.bias.data(), fd); o.table = table_const(layernorm_table(l));
+      o.left = l.ln_multiplier; o.shift = l.ln_range_check_bits; o.d[0] = fd; o.d[1] = l.ln_dim_size; o.out = new_tensor(alen, IQ_NO);
     }
     DP_REQUIRE(p.tensors[(size_t)o.out].len == lens[id], DP_ERR_SHAPE, "dp_model_infer: tensor length");
     p.ops.push_back(o); slot[id] = {o.out};
   }
   for (const Edge& e : output_edges(m)) p.outputs.push_back(tensor_of(e));
+  // (m is the model of the dp_model that keeps this program: it outlives it)
+  p.shifts = [&m](const InferOp& o, const int64_t* x, size_t nb, int64_t* shifts) {
+    const LayerSpec& l = m.layers[(size_t)o.node];
+    return infer_softmax_shifts(l.kind == L_MHA ? mha_softmax_spec(l) : l, x, nb, shifts);
+  };
   return p;
 }
 #endif

@@ -2,12 +2,13 @@
 // build of tests/ cuts its kernels from there). Activations are [batch][tensor] int64, with an int8 copy next to every tensor whose values are
 // known to lie within -128..127 (what a Requant writes, and what ReLU / MaxPool make of it): the int8 copies are the operands of k_infer_gemm_i8.
 // Bad data (a Requant input beyond its bit size, a token outside the vocabulary) raises bits of a device error word with a vector atomic; the
-// host reads it with the outputs. Every launch is finite; nothing here waits for the host.
+// host reads it with the outputs. Every launch is finite; nothing here waits for the host. A Softmax (IO_SOFTMAX) splits the chunk's stream in
+// two: the host reads the error word and the Softmax input, computes one shift per row (InferProgram::shifts) and uploads them.
 
 typedef int infer_v4i __attribute__((ext_vector_type(4)));
 typedef int infer_v16i __attribute__((ext_vector_type(16)));
 constexpr int IG_TM = 64, IG_TN = 64, IG_TK = 64, IG_LD = IG_TK + 16;  // tile of a workgroup (4 waves, 32 x 32 each); LDS row pitch in bytes
-constexpr unsigned INFER_ERR_REQUANT = 1, INFER_ERR_TOKEN = 2;
+constexpr unsigned INFER_ERR_REQUANT = 1, INFER_ERR_TOKEN = 2, INFER_ERR_GELU = 4, INFER_ERR_LN_INPUT = 8, INFER_ERR_LN_TABLE = 16, INFER_ERR_SOFTMAX = 32;
 
 // 16 consecutive int8 of row `row` of X[rows][K] from column k on, zeros outside the matrix. K % 16 == 0: one aligned 16-byte load
 __device__ __forceinline__ infer_v4i infer_ld16(const int8_t* __restrict__ X, size_t rows, size_t K, size_t row, size_t k, bool k16) {
@@ -135,6 +136,64 @@ __global__ __launch_bounds__(256) void k_infer_conv(const int64_t* __restrict__ 
   }
   o[i] = (int64_t)acc;
 }
+// Activation::Gelu (gelu_op): table[v * mult + max], the table's rows being -max .. max - 1. |v| > 2^20 or a scaled value outside the table
+// raises the error word and nothing is read
+__global__ __launch_bounds__(256) void k_infer_gelu(const int64_t* __restrict__ x, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n, int64_t mult, int64_t mx, unsigned* err) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t v = x[i], lim = int64_t(1) << 20;
+  const int64_t scaled = (int64_t)((uint64_t)v * (uint64_t)mult);  // (|v| <= 2^20 and mult <= 2^12 once the first check holds)
+  if (v < -lim || v > lim || scaled < -mx || scaled >= mx) { atomicOr(err, INFER_ERR_GELU); o[i] = 0; return; }
+  o[i] = table[scaled + mx];
+}
+__device__ __forceinline__ uint64_t infer_wave_sum(uint64_t v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d, 64);
+  return v;
+}
+// LayerNorm::evaluate (layernorm_op): one wave per row of fd elements (a power of two; lanes beyond a short row add zeros). 64-bit wrap-around
+// arithmetic as on the host: full = N mult sum(x^2) - mult sum(x)^2, in = full >> rcb (arithmetic), out = gamma (N x - sum) lut[in + 2^14] + beta.
+// |x| > 2^20 anywhere in the row, or `in` outside the table, raises the error word and the row is written as zeros (the table is not read)
+__global__ __launch_bounds__(256) void k_infer_layernorm(const int64_t* __restrict__ x, const int64_t* __restrict__ gamma, const int64_t* __restrict__ beta, const int64_t* __restrict__ lut,
+                                                         int64_t* __restrict__ o, size_t rows, size_t fd, int64_t nn, int64_t mult, unsigned rcb, unsigned* err) {
+  const int lane = threadIdx.x & 63;
+  const size_t row = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= rows) return;  // (the whole wave)
+  const int64_t* xr = x + row * fd;
+  const int64_t lim = int64_t(1) << 20, tmax = int64_t(1) << 14;
+  uint64_t sq = 0, sum = 0; bool bad = false;
+  for (size_t i = lane; i < fd; i += 64) { const int64_t v = xr[i]; bad = bad || v < -lim || v > lim; sq += (uint64_t)v * (uint64_t)v; sum += (uint64_t)v; }
+  sq = infer_wave_sum(sq); sum = infer_wave_sum(sum);
+  unsigned e = __any(bad) ? INFER_ERR_LN_INPUT : 0;
+  const uint64_t n = (uint64_t)nn, m = (uint64_t)mult;
+  const int64_t in = (int64_t)(n * m * sq - m * sum * sum) >> rcb;
+  if (!e && (in < -tmax || in >= tmax)) e = INFER_ERR_LN_TABLE;
+  if (e) {
+    if (lane == 0) atomicOr(err, e);
+    for (size_t i = lane; i < fd; i += 64) o[row * fd + i] = 0;
+    return;
+  }
+  const uint64_t inv = (uint64_t)lut[in + tmax];
+  for (size_t i = lane; i < fd; i += 64) o[row * fd + i] = (int64_t)((uint64_t)gamma[i] * (n * (uint64_t)xr[i] - sum) * inv + (uint64_t)beta[i]);
+}
+// Softmax::evaluate (softmax_op) after the shifts: element j of row i (rows of K words; i counts samples x C x R) is kept when j <= i mod R.
+// |masked| = low byte | high byte | exponential table index (tv bits) | zero chunks (zc groups of zv bits): table[index], times (chunk == 0) for
+// every group. |x| > 2^24 raises the error word (the index is masked: nothing is read outside the table)
+__global__ __launch_bounds__(256) void k_infer_softmax(const int64_t* __restrict__ x, const int64_t* __restrict__ shift, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n,
+                                                       size_t R, size_t K, int64_t scalar, int64_t neg_inf, unsigned tv, unsigned zc, unsigned zv, unsigned* err) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t row = i / K, j = i % K;
+  const int64_t v = x[i], lim = int64_t(1) << 24;
+  if (v < -lim || v > lim) atomicOr(err, INFER_ERR_SOFTMAX);
+  const int64_t masked = j <= row % R ? (int64_t)((uint64_t)v * (uint64_t)scalar + (uint64_t)shift[row]) : neg_inf;
+  int64_t r = masked < 0 ? (int64_t)(0 - (uint64_t)masked) : masked;
+  r >>= 16;
+  int64_t acc = table[r & ((int64_t(1) << tv) - 1)];
+  r >>= tv;
+  for (unsigned z = 0; z < zc; z++) { acc *= (r & ((int64_t(1) << zv) - 1)) == 0 ? 1 : 0; r >>= zv; }
+  o[i] = acc;
+}
 // model input tensor `off .. off + len` of every sample, from the uploaded block (int8 when the host found every word within -128..127, else int64)
 __global__ __launch_bounds__(256) void k_infer_load(const int64_t* __restrict__ s64, const int8_t* __restrict__ s8, size_t stride, size_t off, size_t len, int64_t* __restrict__ o, int8_t* __restrict__ o8, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -180,7 +239,7 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
   st->c64.resize(p.consts.size(), nullptr); st->c8.resize(p.consts.size(), nullptr);
   auto const64 = [&](int c) -> const int64_t* {
     if (c < 0) return nullptr;
-    if (!st->c64[(size_t)c]) { int64_t* dp_ = nullptr; HIP_CHECK(hipMalloc((void**)&dp_, std::max<size_t>(p.consts[(size_t)c].n, 1) * 8)); st->c64[(size_t)c] = dp_; HIP_CHECK(hipMemcpy(dp_, p.consts[(size_t)c].h64, p.consts[(size_t)c].n * 8, hipMemcpyHostToDevice)); }
+    if (!st->c64[(size_t)c]) { int64_t* dp_ = nullptr; HIP_CHECK(hipMalloc((void**)&dp_, std::max<size_t>(p.consts[(size_t)c].n, 1) * 8)); st->c64[(size_t)c] = dp_; HIP_CHECK(hipMemcpy(dp_, p.consts[(size_t)c].data(), p.consts[(size_t)c].n * 8, hipMemcpyHostToDevice)); }
     return st->c64[(size_t)c];
   };
   auto const8 = [&](int c) -> const int8_t* {
@@ -194,13 +253,17 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
   const size_t in_bytes = chunk * p.input_len * (in_q ? 1 : 8), out_words = chunk * p.output_len + 1;
   const size_t off_in = total; total += up(in_bytes);
   const size_t off_out = total; total += up(out_words * 8);
+  // the shift step of a Softmax on the host side: [its input of the chunk][the error word][the shifts]
+  size_t sm_in = 0, sm_sh = 0;
+  for (const InferOp& o : p.ops) if (o.kind == IO_SOFTMAX) { sm_in = std::max(sm_in, up(chunk * p.tensors[(size_t)o.in0].len * 8)); sm_sh = std::max(sm_sh, chunk * p.tensors[(size_t)o.in1].len * 8); }
   char* scratch = nullptr; char* pinned = nullptr;
-  size_t launches[IO_KINDS + 2] = {0}, n_i8 = 0, n_i64 = 0, nchunks = 0;
+  size_t launches[IO_KINDS + 2] = {0}, n_i8 = 0, n_i64 = 0, nchunks = 0, trips = 0;
+  double trip_ms = 0;
   unsigned err = 0;
   auto cleanup = [&] { (void)hipStreamSynchronize(s); if (scratch) (void)hipFree(scratch); if (pinned) (void)hipHostFree(pinned); scratch = pinned = nullptr; };
   try {
     HIP_CHECK(hipMalloc((void**)&scratch, total));
-    HIP_CHECK(hipHostMalloc((void**)&pinned, std::max(in_bytes, out_words * 8), hipHostMallocDefault));
+    HIP_CHECK(hipHostMalloc((void**)&pinned, std::max(std::max(in_bytes, out_words * 8), sm_in + 256 + sm_sh), hipHostMallocDefault));
     auto T64 = [&](int t) { return (int64_t*)(scratch + off64[(size_t)t]); };
     auto T8 = [&](int t) { return q[(size_t)t] ? (int8_t*)(scratch + off8[(size_t)t]) : (int8_t*)nullptr; };
     int64_t* dout = (int64_t*)(scratch + off_out);
@@ -219,6 +282,7 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
         ioff += len; launches[IO_KINDS]++;
       }
       for (const InferOp& o : p.ops) {
+        if (err) break;
         const size_t n = nb * p.tensors[(size_t)o.out].len;
         launches[o.kind]++;
         switch (o.kind) {
@@ -245,9 +309,35 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
           case IO_EMBED: k_infer_embed<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.w), T64(o.out), n, o.d[0], o.d[1], derr); break;
           case IO_MAXPOOL: k_infer_maxpool<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.out), T8(o.out), n, o.d[1], o.d[2]); break;
           case IO_CONV: k_infer_conv<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.w), const64(o.bias), T64(o.out), n, o.d[0], o.d[1], o.d[2], o.d[3], o.d[4], o.d[5], o.d[6]); break;
+          case IO_GELU: k_infer_gelu<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.table), T64(o.out), n, o.left, (int64_t)o.d[0], derr); break;
+          case IO_LAYERNORM: {
+            const size_t rows = n / o.d[0];
+            k_infer_layernorm<<<grid(rows * 64), 256, 0, s>>>(T64(o.in0), const64(o.w), const64(o.bias), const64(o.table), T64(o.out), rows, o.d[0], (int64_t)o.d[1], o.left, o.shift, derr);
+            break;
+          }
+          case IO_SOFTMAX: {
+            // the shift of every row is made on the host, by the function the host inference calls. The error word comes first: rows that follow
+            // bad data are not read
+            const auto ts = std::chrono::steady_clock::now();
+            const size_t nx = nb * p.tensors[(size_t)o.in0].len, nsh = nb * p.tensors[(size_t)o.in1].len;
+            const int64_t* table = const64(o.table);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(pinned + sm_in, derr, 8, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(pinned, T64(o.in0), nx * 8, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            err = *(const unsigned*)(pinned + sm_in);
+            if (!err && !p.shifts(o, (const int64_t*)pinned, nb, (int64_t*)(pinned + sm_in + 256))) err = INFER_ERR_SOFTMAX;
+            if (!err) {
+              HIP_CHECK(hipMemcpyAsync(T64(o.in1), pinned + sm_in + 256, nsh * 8, hipMemcpyHostToDevice, s));
+              k_infer_softmax<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.in1), table, T64(o.out), n, o.d[1], o.d[2], o.left, -(((o.right >> 16) + 1) << 16), o.bits, (unsigned)o.d[3], (unsigned)o.d[4], derr);
+            }
+            trips++; trip_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
+            break;
+          }
           default: throw DpError(DP_ERR_ARG, "dp_model_infer: unknown op");
         }
       }
+      if (err) { nchunks++; break; }
       size_t ooff = 0;
       for (int t : p.outputs) {
         const size_t len = p.tensors[(size_t)t].len, n = nb * len;
@@ -267,9 +357,13 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
   cleanup();
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (wall_ms) *wall_ms = ms;
-  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu conv %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms\n",
-                   n_i8, n_i64, launches[IO_CONV], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1],
+  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu conv %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms\n",
+                   n_i8, n_i64, launches[IO_CONV], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], trips, trip_ms,
                    ninputs, nchunks, chunk, (double)total / 1048576.0, in_q ? "int8" : "int64", ms);
   DP_REQUIRE(!(err & INFER_ERR_REQUANT), DP_ERR_ARG, "requant: value exceeds intermediate bit size");
   DP_REQUIRE(!(err & INFER_ERR_TOKEN), DP_ERR_ARG, "embeddings: token outside the vocabulary");
+  DP_REQUIRE(!(err & INFER_ERR_GELU), DP_ERR_ARG, "gelu: input out of range");
+  DP_REQUIRE(!(err & INFER_ERR_LN_INPUT), DP_ERR_ARG, "layernorm: input out of range");
+  DP_REQUIRE(!(err & INFER_ERR_LN_TABLE), DP_ERR_ARG, "layernorm: the inverse square root input leaves its table");
+  DP_REQUIRE(!(err & INFER_ERR_SOFTMAX), DP_ERR_ARG, "softmax: input out of range");
 }

@@ -286,20 +286,25 @@ struct SoftmaxTrace {
   std::vector<int64_t> shift, shifted_input, tril, bias, low, high, exp_in, exp_out, row_sums;
   std::vector<std::vector<int64_t>> zero_in, zero_out;
 };
+// the shift of one row whose first `take` entries the causal mask keeps (the entries already range checked). The only data-dependent floating
+// point of the inference: softmax_op and the shift step of dp_model_infer_ex (infer.h) both call it, so the two paths share its roundings
+inline int64_t softmax_row_shift(const LayerSpec& l, const int64_t* row, size_t take) {
+  if (take == 1) return -row[0] * l.sm_scalar;
+  float inv_temp, in_scale; memcpy(&inv_temp, &l.sm_temp_bits, 4); memcpy(&in_scale, &l.sm_in_scale_bits, 4);
+  int64_t mx = row[0]; for (size_t j = 1; j < take; j++) mx = std::max(mx, row[j]);
+  float sum = 0.0f;
+  for (size_t j = 0; j < take; j++) sum += expf(((float)(row[j] - mx) * in_scale) / inv_temp);
+  return -(int64_t)roundf((float)(1u << SM_LOG_SCALE) * inv_temp * logf(sum)) - mx * l.sm_scalar;
+}
 inline std::vector<int64_t> softmax_op(const LayerSpec& l, const std::vector<int64_t>& x, SoftmaxTrace* out) {
   const size_t C = l.sm_shape[0], R = l.sm_shape[1], K = l.sm_shape[2];
   DP_REQUIRE(C && R && R == K && x.size() == C * R * K, DP_ERR_SHAPE, "softmax: shapes");
-  float inv_temp, in_scale; memcpy(&inv_temp, &l.sm_temp_bits, 4); memcpy(&in_scale, &l.sm_in_scale_bits, 4);
   SoftmaxTrace d;
   const int64_t neg_inf = -(((l.sm_bkm >> 16) + 1) << 16);
   for (size_t i = 0; i < C * R; i++) {
     const int64_t* row = &x[i * K]; const size_t take = i % R + 1;
     for (size_t j = 0; j < K; j++) DP_REQUIRE(row[j] >= -(int64_t(1) << 24) && row[j] <= (int64_t(1) << 24), DP_ERR_ARG, "softmax: input out of range");
-    if (i % R == 0) { d.shift.push_back(-row[0] * l.sm_scalar); continue; }
-    int64_t mx = row[0]; for (size_t j = 1; j < take; j++) mx = std::max(mx, row[j]);
-    float sum = 0.0f;
-    for (size_t j = 0; j < take; j++) sum += expf(((float)(row[j] - mx) * in_scale) / inv_temp);
-    d.shift.push_back(-(int64_t)roundf((float)(1u << SM_LOG_SCALE) * inv_temp * logf(sum)) - mx * l.sm_scalar);
+    d.shift.push_back(softmax_row_shift(l, row, take));
   }
   d.tril.resize(x.size()); d.bias.resize(x.size()); d.shifted_input.resize(x.size());
   for (size_t i = 0; i < C * R; i++) for (size_t j = 0; j < K; j++) {

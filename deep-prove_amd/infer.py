@@ -1,4 +1,4 @@
-"""Batched quantised inference on the device: ctypes binding of include/deep_prove_hip_infer.h (dp_model_infer). The entry point has a header and a
+"""Batched quantised inference on the device: ctypes binding of include/deep_prove_hip_infer.h (dp_model_infer, dp_model_infer_ex). The entry points have a header and a
 binding table of its own: `_lib.SIGNATURES` lists exactly the symbols of include/deep_prove_hip.h."""
 import ctypes as C
 
@@ -10,7 +10,9 @@ from ._lib import check, i64p, vp
 # name -> (restype, argtypes): every symbol declared in include/deep_prove_hip_infer.h
 INFER_SIGNATURES = {
     "dp_model_infer": (C.c_int32, [vp, i64p, C.c_size_t, C.c_size_t, i64p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_double)]),
+    "dp_model_infer_ex": (C.c_int32, [vp, i64p, C.c_size_t, C.c_size_t, C.c_uint32, i64p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_double)]),
 }
+ALL_KINDS = 1  # DP_INFER_ALL_KINDS
 
 _bound = None
 
@@ -27,9 +29,10 @@ def _load():
     return _bound
 
 
-def infer(ctx, inputs_i64):
+def infer(ctx, inputs_i64, all_kinds=False, flags=None):
     """Model::run for every row of inputs_i64[n, ninput] on the context's GPU; returns (outputs[n, nout], wall_ms). The integers are those of
-    infer_host, row by row. Models with LayerNorm / Softmax / Mha / GELU nodes raise DeepProveError (DP_ERR_ARG)."""
+    infer_host, row by row. Models with LayerNorm / Softmax / Mha / GELU nodes raise DeepProveError (DP_ERR_ARG) unless all_kinds is set
+    (dp_model_infer_ex with DP_INFER_ALL_KINDS: the Softmax row shifts are computed on the host). flags: the raw flag word, instead of all_kinds."""
     lib = _load()
     x = np.ascontiguousarray(inputs_i64, dtype=np.int64)
     if x.ndim == 1:
@@ -40,5 +43,7 @@ def infer(ctx, inputs_i64):
     outs = np.empty((n, cap.value), dtype=np.int64)
     no = C.c_size_t(0)
     ms = C.c_double()
-    check(lib.dp_model_infer(ctx.h, x.ctypes.data_as(i64p), n, ninput, outs.ctypes.data_as(i64p), cap.value, C.byref(no), C.byref(ms)))
+    if flags is None:
+        flags = ALL_KINDS if all_kinds else 0
+    check(lib.dp_model_infer_ex(ctx.h, x.ctypes.data_as(i64p), n, ninput, flags, outs.ctypes.data_as(i64p), cap.value, C.byref(no), C.byref(ms)))
     return outs[:, :no.value].copy(), ms.value

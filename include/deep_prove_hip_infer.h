@@ -3,17 +3,28 @@
  * Types, status codes and conventions are those of deep_prove_hip.h (included below): int32 status, nothing throws or aborts across
  * the ABI, dp_last_error() carries the message. No status code is added here.
  *
- * Layer coverage: Dense, Requant, ReLU, Conv, MaxPool, Flatten, MatMul (constant matrix, bias, TransposeB), Add with a static operand,
- * Embeddings, Positional::Learned, MatMul / Add of two inputs, ConcatMatMul and QKV (layer kinds 0-13), in chain blobs and graph blobs with
- * several input and output tensors. A model that holds a LayerNorm, Softmax, Mha or GELU node (kinds 14-17) is refused with DP_ERR_ARG before
- * any device work — the message names the node and the kind: their tables are made in floating point and Softmax shifts its rows by logf,
- * which a device libm does not reproduce bit for bit. They are a follow-up; dp_model_infer_host covers them meanwhile.
+ * Layer coverage of dp_model_infer (and of dp_model_infer_ex without flags): Dense, Requant, ReLU, Conv, MaxPool, Flatten, MatMul (constant
+ * matrix, bias, TransposeB), Add with a static operand, Embeddings, Positional::Learned, MatMul / Add of two inputs, ConcatMatMul and QKV
+ * (layer kinds 0-13), in chain blobs and graph blobs with several input and output tensors. A model that holds a LayerNorm, Softmax, Mha or
+ * GELU node (kinds 14-17) is refused with DP_ERR_ARG before any device work — the message names the node and the kind.
  *
- * Errors in the data are the host's: a Requant input beyond 2^intermediate_bit_size or an Embeddings token outside the vocabulary makes the
- * whole call return DP_ERR_ARG (as dp_model_infer_host does for that input); the model stays usable.
+ * dp_model_infer_ex with DP_INFER_ALL_KINDS covers every kind the prover accepts. The tables of the four kinds (GELU, inverse square root,
+ * Softmax exponential) are made in f32 with the host's libm: they belong to the model, so the host builds them once with the functions the
+ * prover uses and uploads them, and LayerNorm, GELU and the table part of Softmax are integer work on the device. The shift of a Softmax row
+ * is minus the logarithm of a sum of exponentials in f32, which a device libm does not reproduce bit for bit: it is computed ON THE HOST, by
+ * the function dp_model_infer_host calls. At every Softmax (one per Softmax or Mha node) and chunk of the batch the device hands the Softmax
+ * input to the host, the host computes one shift per row on up to min(DP_HOST_THREADS, 16) threads and the device goes on: one round trip
+ * each, counted in the `[dp infer]` line.
+ *
+ * Errors in the data are the host's: a Requant input beyond 2^intermediate_bit_size, an Embeddings token outside the vocabulary and, under
+ * DP_INFER_ALL_KINDS, a GELU input beyond 2^20 or outside its table ("gelu: ..."), a LayerNorm input beyond 2^20 or a row whose variance leaves
+ * the inverse-square-root table ("layernorm: ..."), a Softmax input beyond 2^24 ("softmax: ...") make the whole call return DP_ERR_ARG (as
+ * dp_model_infer_host does for that input); the model stays usable. The device error word is read before the host computes any shift, so no
+ * row that follows bad data reaches expf. Flag bits other than DP_INFER_ALL_KINDS: DP_ERR_ARG.
  *
  * Knobs (environment): DP_INFER_SCRATCH_MB (activation scratch of one chunk of the batch, default 1024), DP_INFER_NO_MFMA=1 (64-bit
- * products everywhere), DP_INFER_LOG=1 (one `[dp infer]` line per call on stderr: launches per kernel, chunks, wall time).
+ * products everywhere), DP_INFER_LOG=1 (one `[dp infer]` line per call on stderr: launches per kernel, chunks, wall time; gelu / layernorm / softmax launches,
+ * shift_trips = round trips of the Softmax shift step and shift_ms = the milliseconds spent in them).
  */
 #ifndef DEEP_PROVE_HIP_INFER_H
 #define DEEP_PROVE_HIP_INFER_H
@@ -27,6 +38,12 @@ extern "C" {
  * Integers are exactly those of dp_model_infer_host, input by input. Not to be called while a prove call of the same model runs. */
 int32_t dp_model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput,
                        int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms);
+
+#define DP_INFER_ALL_KINDS 1u   /* also LayerNorm, Softmax, Mha, GELU (kinds 14-17) */
+/* dp_model_infer with a flag word: 0 = exactly dp_model_infer (the same refusal included); DP_INFER_ALL_KINDS as described above. The flattened
+ * model is kept per flag word. */
+int32_t dp_model_infer_ex(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags,
+                          int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms);
 
 #ifdef __cplusplus
 }
