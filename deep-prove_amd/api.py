@@ -570,6 +570,12 @@ class Context:
         from .infer import infer
         return infer(self, inputs_i64, all_kinds=all_kinds)
 
+    def infer_checked(self, inputs_i64, all_kinds=False):
+        """dp_model_infer_checked: infer() that refuses bad data input by input; returns (outputs[n, nout], reasons[n], wall_ms) — reasons[i] == 0:
+        row i is inferred; otherwise the class (deep_prove_amd.infer.REASONS) of the first node at which the host refuses input i, and row i is zeros"""
+        from .infer import infer_checked
+        return infer_checked(self, inputs_i64, all_kinds=all_kinds)
+
     def free(self):
         if self.h:
             _lib.load().dp_model_free(self.h)
@@ -613,6 +619,21 @@ class Prover:
                                        outs.ctypes.data_as(i64p), cap, C.byref(no), C.byref(ms)))
         proofs = [_take(pws[i], pns[i]) for i in range(nproofs)]
         return proofs, outs[:, :no.value].copy(), ms.value
+
+    def prove_batch_screened(self, inputs_i64, concurrency):
+        """prove_batch that survives inputs the inference refuses (prove_batch raises on the whole batch for one of them): the batch is screened on
+        the device (Context.infer_checked, all kinds) and the rows with reason 0 go to prove_batch — which is not called when there are none.
+        Returns (proofs, outputs[n, nout], reasons[n], wall_ms of the proving); proofs[i] is None and outputs[i] zeros where reasons[i] != 0"""
+        x = np.ascontiguousarray(inputs_i64, dtype=np.int64)
+        screened, reasons, _ = self.ctx.infer_checked(x, all_kinds=True)
+        good = np.flatnonzero(reasons == 0)
+        proofs, outs, ms = [None] * x.shape[0], np.zeros_like(screened), 0.0
+        if good.size:
+            ps, os_, ms = self.prove_batch(x[good], concurrency)
+            for k, i in enumerate(good):
+                proofs[i] = ps[k]
+            outs[good] = os_
+        return proofs, outs, reasons, ms
 
 
     def output_len(self):

@@ -9,6 +9,10 @@
 // computation that depends on the data, the shift of a Softmax row, stays on the host: at an IO_SOFTMAX hip_infer_run downloads the input of
 // the chunk, calls InferProgram::shifts (infer_softmax_shifts below: softmax_row_shift of zkml.h, the function softmax_op calls) and uploads
 // one shift per row. An Mha node is three ops: the product Q K^T, the Softmax, the product with V.
+// Checked mode (dp_model_infer_checked: hip_infer_run with `reasons`) refuses inputs one by one instead of the call: one status word per sample
+// of the chunk holds the class (INFER_BAD_*) of the first op that refused it; the shift step works sample by sample (InferProgram::shifts_checked,
+// infer_softmax_shifts_checked below) and never reads the rows of a sample that is already refused. Program and constants are those of the
+// plain call with the same flag word.
 #pragma once
 #include "dev.h"
 #include <algorithm>
@@ -32,6 +36,8 @@ struct InferConst {
   const int64_t* data() const { return own.empty() ? h64 : own.data(); }
 };
 constexpr uint32_t INFER_ALL_KINDS = 1;  // (DP_INFER_ALL_KINDS of the public header)
+// the status of one input in checked mode (DP_INFER_OK, DP_INFER_BAD_* of the public header): which kind of node refused it first
+constexpr uint32_t INFER_OK = 0, INFER_BAD_REQUANT = 1, INFER_BAD_TOKEN = 2, INFER_BAD_GELU = 3, INFER_BAD_LAYERNORM = 4, INFER_BAD_SOFTMAX = 5;
 enum InferOpKind { IO_GEMM = 0, IO_GEMM2, IO_REQUANT, IO_RELU, IO_ADDC, IO_ADD2, IO_EMBED, IO_MAXPOOL, IO_CONV, IO_GELU, IO_LAYERNORM, IO_SOFTMAX, IO_KINDS };
 // out[b][c*sOc + r*sOr + n*sOn] = sum_m A[b][c*sAc + r*sAr + m*sAm] * B[(B a tensor: b)][c*sBc + m*sBm + n*sBn] (+ bias[n])
 struct InferGemmShape { size_t C = 1, R = 0, K = 0, N = 0; size_t sAc = 0, sAr = 0, sAm = 0, sBc = 0, sBm = 0, sBn = 0, sOc = 0, sOr = 0, sOn = 0; };
@@ -55,12 +61,17 @@ struct InferProgram {
   std::vector<InferOp> ops;
   // the shift step of an IO_SOFTMAX: x = its input for nb samples; shifts: nb x C * R words. False: an input beyond 2^24 (no shift is made of such a sample)
   std::function<bool(const InferOp& o, const int64_t* x, size_t nb, int64_t* shifts)> shifts;
+  // the same step sample by sample (checked mode). status: nb words; a sample whose word is set is not read and gets zero shifts, a sample with an
+  // input beyond 2^24 gets INFER_BAD_SOFTMAX and zero shifts
+  std::function<void(const InferOp& o, const int64_t* x, size_t nb, int64_t* shifts, uint32_t* status)> shifts_checked;
 };
 struct InferDeviceState;  // the constants on the device (made at the first call, freed with the model)
 InferDeviceState* hip_infer_state_new(int device);
 void hip_infer_state_free(InferDeviceState* s);
 // inputs: ninputs x p.input_len words; outputs: ninputs x out_stride words (the first p.output_len of each row are written). Throws DpError.
-void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* inputs, size_t ninputs, int64_t* outputs, size_t out_stride, double* wall_ms);
+// reasons (ninputs words) not null: checked mode — bad data refuses its input (reasons[i] = INFER_BAD_*, the output row zeros), not the call, and
+// every chunk is processed.
+void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* inputs, size_t ninputs, int64_t* outputs, size_t out_stride, double* wall_ms, uint32_t* reasons = nullptr);
 
 #ifdef DP_INFER_PLANNER  // (capi.cpp, after zkml.h)
 inline const char* infer_kind_name(int k) {
@@ -89,6 +100,30 @@ inline bool infer_softmax_shifts(const LayerSpec& sm, const int64_t* x, size_t n
   part(0);
   for (std::thread& t : th) t.join();
   return ok;
+}
+// the same step sample by sample (checked mode), on as many threads. A sample whose status word is set was refused by an earlier op: its rows
+// hold whatever the later kernels made of it and are NOT read (no value of theirs reaches expf, logf or the conversion to an integer); it gets
+// zero shifts. Every other sample is range checked as a whole before its first shift is made — softmax_op's order — and gets INFER_BAD_SOFTMAX
+// and zero shifts when an element lies beyond 2^24
+inline void infer_softmax_shifts_checked(const LayerSpec& sm, const int64_t* x, size_t nb, int64_t* shifts, uint32_t* status) {
+  const size_t C = sm.sm_shape[0], R = sm.sm_shape[1], K = sm.sm_shape[2], rows = C * R;
+  const char* te = getenv("DP_HOST_THREADS");
+  size_t nth = te ? (size_t)std::max(1, atoi(te)) : (size_t)std::max(1.0, host_cpu_budget() - 2.0);
+  nth = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(std::min<size_t>(nth, 16), nb * rows / 256), nb));
+  auto part = [&](size_t t) {
+    for (size_t b = nb * t / nth, e = nb * (t + 1) / nth; b < e; b++) {
+      const int64_t* xs = x + b * rows * K;
+      int64_t* sh = shifts + b * rows;
+      bool in = !status[b];
+      for (size_t j = 0; j < rows * K && in; j++) in = xs[j] >= -(int64_t(1) << 24) && xs[j] <= (int64_t(1) << 24);
+      if (!in) { if (!status[b]) status[b] = INFER_BAD_SOFTMAX; std::fill(sh, sh + rows, int64_t(0)); continue; }
+      for (size_t i = 0; i < rows; i++) sh[i] = softmax_row_shift(sm, xs + i * K, i % R + 1);
+    }
+  };
+  std::vector<std::thread> th;
+  for (size_t t = 1; t < nth; t++) th.emplace_back(part, t);
+  part(0);
+  for (std::thread& t : th) t.join();
 }
 inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
   for (size_t id = 0; id < m.layers.size(); id++) {
@@ -244,6 +279,10 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
   p.shifts = [&m](const InferOp& o, const int64_t* x, size_t nb, int64_t* shifts) {
     const LayerSpec& l = m.layers[(size_t)o.node];
     return infer_softmax_shifts(l.kind == L_MHA ? mha_softmax_spec(l) : l, x, nb, shifts);
+  };
+  p.shifts_checked = [&m](const InferOp& o, const int64_t* x, size_t nb, int64_t* shifts, uint32_t* status) {
+    const LayerSpec& l = m.layers[(size_t)o.node];
+    infer_softmax_shifts_checked(l.kind == L_MHA ? mha_softmax_spec(l) : l, x, nb, shifts, status);
   };
   return p;
 }

@@ -4,12 +4,31 @@
 // Bad data (a Requant input beyond its bit size, a token outside the vocabulary) raises bits of a device error word with a vector atomic; the
 // host reads it with the outputs. Every launch is finite; nothing here waits for the host. A Softmax (IO_SOFTMAX) splits the chunk's stream in
 // two: the host reads the error word and the Softmax input, computes one shift per row (InferProgram::shifts) and uploads them.
+// Checked mode (dp_model_infer_checked: `status` not null in the five kernels that can refuse data) keeps one status word per sample of the
+// chunk instead: the class (INFER_BAD_* of infer.h) of the first op that refused the sample. Ops run in stream order and the word only ever
+// goes from zero to a class (compare-and-swap), so whatever later ops make of a refused sample's values cannot change it. Those values travel
+// on; the guards that keep every kernel inside its tables and buffers on such data are named at each kernel.
 
 typedef int infer_v4i __attribute__((ext_vector_type(4)));
 typedef int infer_v16i __attribute__((ext_vector_type(16)));
 constexpr int IG_TM = 64, IG_TN = 64, IG_TK = 64, IG_LD = IG_TK + 16;  // tile of a workgroup (4 waves, 32 x 32 each); LDS row pitch in bytes
 constexpr unsigned INFER_ERR_REQUANT = 1, INFER_ERR_TOKEN = 2, INFER_ERR_GELU = 4, INFER_ERR_LN_INPUT = 8, INFER_ERR_LN_TABLE = 16, INFER_ERR_SOFTMAX = 32;
 
+// Checked mode: sample `s` is refused with class `cls` unless an earlier op (or an earlier wave of this one: same class) refused it. The plain
+// load keeps the atomics of a sample that is bad everywhere to the few waves that run before the first of them lands
+__device__ __forceinline__ void infer_refuse(unsigned* status, size_t s, unsigned cls) {
+  if (__hip_atomic_load(status + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) atomicCAS(status + s, 0u, cls);
+}
+// What an element-wise kernel does with `bad` (element i of a tensor of `per` words per sample; every lane of the wave that has an element calls
+// it, in converged control flow). Plain mode: the bit of the chunk's error word. Checked mode: one wave-wide vote — nothing more on good data —
+// and then one atomic per run of bad lanes and sample, from the first lane of the run (a wave of 64 consecutive elements can straddle samples)
+__device__ __forceinline__ void infer_flag(bool bad, size_t i, size_t per, unsigned* status, unsigned cls, unsigned* err, unsigned bit) {
+  if (!status) { if (bad) atomicOr(err, bit); return; }
+  const unsigned long long m = __ballot(bad);
+  if (!m) return;
+  const unsigned lane = threadIdx.x & 63;
+  if (bad && (lane == 0 || !((m >> (lane - 1)) & 1) || i % per == 0)) infer_refuse(status, i / per, cls);
+}
 // 16 consecutive int8 of row `row` of X[rows][K] from column k on, zeros outside the matrix. K % 16 == 0: one aligned 16-byte load
 __device__ __forceinline__ infer_v4i infer_ld16(const int8_t* __restrict__ X, size_t rows, size_t K, size_t row, size_t k, bool k16) {
   infer_v4i v = {0, 0, 0, 0};
@@ -75,12 +94,15 @@ __global__ __launch_bounds__(256) void k_infer_gemm_i64(const int64_t* __restric
   O[b * lenO + c * g.sOc + r * g.sOr + n * g.sOn] = (int64_t)acc;
 }
 // Requant::apply: (v * mult + 2^(sh-1)) >> sh clamped to +-127; |v| > 2^bits raises the error word (the host refuses the whole call, as run_model does)
-__global__ __launch_bounds__(256) void k_infer_requant(const int64_t* __restrict__ x, int64_t* __restrict__ o, int8_t* __restrict__ o8, size_t n, int64_t mult, unsigned sh, unsigned bits, unsigned* err) {
+// or, in checked mode, refuses the sample (per = words per sample). A refused sample's output is clamped like any other: its int8 copy stays a
+// valid operand of k_infer_gemm_i8
+__global__ __launch_bounds__(256) void k_infer_requant(const int64_t* __restrict__ x, int64_t* __restrict__ o, int8_t* __restrict__ o8, size_t n, int64_t mult, unsigned sh, unsigned bits, unsigned* err,
+                                                       unsigned* status, size_t per) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t v = x[i];
   const uint64_t mag = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
-  if (mag > (uint64_t(1) << bits)) atomicOr(err, INFER_ERR_REQUANT);
+  infer_flag(mag > (uint64_t(1) << bits), i, per, status, INFER_BAD_REQUANT, err, INFER_ERR_REQUANT);
   int64_t y = (int64_t)((uint64_t)v * (uint64_t)mult + (uint64_t(1) << (sh - 1))) >> sh;
   y = y < -127 ? -127 : y > 127 ? 127 : y;
   o[i] = y;
@@ -102,12 +124,16 @@ __global__ __launch_bounds__(256) void k_infer_add2(const int64_t* __restrict__ 
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) o[i] = (int64_t)((uint64_t)left * (uint64_t)x[i] + (uint64_t)right * (uint64_t)y[i]);
 }
-// Embeddings: row tok[t] of the [vocab][emb] table for every token; a token outside the vocabulary raises the error word (and reads row 0)
-__global__ __launch_bounds__(256) void k_infer_embed(const int64_t* __restrict__ tok, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n, size_t vocab, size_t emb, unsigned* err) {
+// Embeddings: row tok[t] of the [vocab][emb] table for every token; a token outside the vocabulary raises the error word, or refuses the sample
+// in checked mode (per = output words per sample), and reads row 0: the table is never read outside its rows, whatever the token
+__global__ __launch_bounds__(256) void k_infer_embed(const int64_t* __restrict__ tok, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n, size_t vocab, size_t emb, unsigned* err,
+                                                     unsigned* status, size_t per) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int64_t t = tok[i / emb];
-  if (t < 0 || (uint64_t)t >= vocab) { atomicOr(err, INFER_ERR_TOKEN); t = 0; }
+  const bool bad = t < 0 || (uint64_t)t >= vocab;
+  infer_flag(bad, i, per, status, INFER_BAD_TOKEN, err, INFER_ERR_TOKEN);
+  if (bad) t = 0;
   o[i] = table[(size_t)t * emb + i % emb];
 }
 // MaxPool 2 x 2, stride 2, on [batch][c][h][w]
@@ -137,13 +163,17 @@ __global__ __launch_bounds__(256) void k_infer_conv(const int64_t* __restrict__ 
   o[i] = (int64_t)acc;
 }
 // Activation::Gelu (gelu_op): table[v * mult + max], the table's rows being -max .. max - 1. |v| > 2^20 or a scaled value outside the table
-// raises the error word and nothing is read
-__global__ __launch_bounds__(256) void k_infer_gelu(const int64_t* __restrict__ x, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n, int64_t mult, int64_t mx, unsigned* err) {
+// raises the error word (checked mode: refuses the sample, per = words per sample) and nothing is read: the same test guards the table against
+// the values of a sample refused earlier
+__global__ __launch_bounds__(256) void k_infer_gelu(const int64_t* __restrict__ x, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n, int64_t mult, int64_t mx, unsigned* err,
+                                                    unsigned* status, size_t per) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t v = x[i], lim = int64_t(1) << 20;
   const int64_t scaled = (int64_t)((uint64_t)v * (uint64_t)mult);  // (|v| <= 2^20 and mult <= 2^12 once the first check holds)
-  if (v < -lim || v > lim || scaled < -mx || scaled >= mx) { atomicOr(err, INFER_ERR_GELU); o[i] = 0; return; }
+  const bool bad = v < -lim || v > lim || scaled < -mx || scaled >= mx;
+  infer_flag(bad, i, per, status, INFER_BAD_GELU, err, INFER_ERR_GELU);
+  if (bad) { o[i] = 0; return; }
   o[i] = table[scaled + mx];
 }
 __device__ __forceinline__ uint64_t infer_wave_sum(uint64_t v) {
@@ -153,9 +183,11 @@ __device__ __forceinline__ uint64_t infer_wave_sum(uint64_t v) {
 }
 // LayerNorm::evaluate (layernorm_op): one wave per row of fd elements (a power of two; lanes beyond a short row add zeros). 64-bit wrap-around
 // arithmetic as on the host: full = N mult sum(x^2) - mult sum(x)^2, in = full >> rcb (arithmetic), out = gamma (N x - sum) lut[in + 2^14] + beta.
-// |x| > 2^20 anywhere in the row, or `in` outside the table, raises the error word and the row is written as zeros (the table is not read)
+// |x| > 2^20 anywhere in the row, or `in` outside the table, raises the error word and the row is written as zeros (the table is not read: the
+// test on `in` is the guard for the rows of a sample refused earlier, too). Checked mode: lane 0 refuses the sample of the row (per = rows per
+// sample; a wave never straddles samples here, the vote is the __any below)
 __global__ __launch_bounds__(256) void k_infer_layernorm(const int64_t* __restrict__ x, const int64_t* __restrict__ gamma, const int64_t* __restrict__ beta, const int64_t* __restrict__ lut,
-                                                         int64_t* __restrict__ o, size_t rows, size_t fd, int64_t nn, int64_t mult, unsigned rcb, unsigned* err) {
+                                                         int64_t* __restrict__ o, size_t rows, size_t fd, int64_t nn, int64_t mult, unsigned rcb, unsigned* err, unsigned* status, size_t per) {
   const int lane = threadIdx.x & 63;
   const size_t row = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;  // (the whole wave)
@@ -169,7 +201,7 @@ __global__ __launch_bounds__(256) void k_infer_layernorm(const int64_t* __restri
   const int64_t in = (int64_t)(n * m * sq - m * sum * sum) >> rcb;
   if (!e && (in < -tmax || in >= tmax)) e = INFER_ERR_LN_TABLE;
   if (e) {
-    if (lane == 0) atomicOr(err, e);
+    if (lane == 0) { if (status) infer_refuse(status, row / per, INFER_BAD_LAYERNORM); else atomicOr(err, e); }
     for (size_t i = lane; i < fd; i += 64) o[row * fd + i] = 0;
     return;
   }
@@ -178,14 +210,16 @@ __global__ __launch_bounds__(256) void k_infer_layernorm(const int64_t* __restri
 }
 // Softmax::evaluate (softmax_op) after the shifts: element j of row i (rows of K words; i counts samples x C x R) is kept when j <= i mod R.
 // |masked| = low byte | high byte | exponential table index (tv bits) | zero chunks (zc groups of zv bits): table[index], times (chunk == 0) for
-// every group. |x| > 2^24 raises the error word (the index is masked: nothing is read outside the table)
+// every group. |x| > 2^24 raises the error word (the index is masked: nothing is read outside the table, for any x and any shift). Checked mode
+// (per = words per sample): the host's shift step has already refused such a sample, or found it refused and given it zero shifts — the test
+// here then leaves its word as it is
 __global__ __launch_bounds__(256) void k_infer_softmax(const int64_t* __restrict__ x, const int64_t* __restrict__ shift, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n,
-                                                       size_t R, size_t K, int64_t scalar, int64_t neg_inf, unsigned tv, unsigned zc, unsigned zv, unsigned* err) {
+                                                       size_t R, size_t K, int64_t scalar, int64_t neg_inf, unsigned tv, unsigned zc, unsigned zv, unsigned* err, unsigned* status, size_t per) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const size_t row = i / K, j = i % K;
   const int64_t v = x[i], lim = int64_t(1) << 24;
-  if (v < -lim || v > lim) atomicOr(err, INFER_ERR_SOFTMAX);
+  infer_flag(v < -lim || v > lim, i, per, status, INFER_BAD_SOFTMAX, err, INFER_ERR_SOFTMAX);
   const int64_t masked = j <= row % R ? (int64_t)((uint64_t)v * (uint64_t)scalar + (uint64_t)shift[row]) : neg_inf;
   int64_t r = masked < 0 ? (int64_t)(0 - (uint64_t)masked) : masked;
   r >>= 16;
@@ -216,7 +250,7 @@ struct InferDeviceState {
 InferDeviceState* hip_infer_state_new(int device) { InferDeviceState* s = new InferDeviceState(); s->device = device; return s; }
 void hip_infer_state_free(InferDeviceState* s) { delete s; }
 
-void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* inputs, size_t ninputs, int64_t* outputs, size_t out_stride, double* wall_ms) {
+void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* inputs, size_t ninputs, int64_t* outputs, size_t out_stride, double* wall_ms, uint32_t* reasons) {
   HipDev* hd = static_cast<HipDev*>(d);
   hd->bind_thread(); hd->sync();
   hipStream_t s = hd->stream();
@@ -247,34 +281,39 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
     return st->c8[(size_t)c];
   };
   // scratch of one chunk (outside the arenas, released before the call returns): [tensors, int64 | int8][input block][output block][error word]
+  // [checked mode: one status word per sample]
+  const bool checked = reasons != nullptr;
+  const size_t stat_bytes = checked ? chunk * 4 : 0;
   std::vector<size_t> off64(nt), off8(nt);
   size_t total = 0;
   for (size_t t = 0; t < nt; t++) { off64[t] = total; total += up(chunk * p.tensors[t].len * 8); off8[t] = total; if (q[t]) total += up(chunk * p.tensors[t].len); }
   const size_t in_bytes = chunk * p.input_len * (in_q ? 1 : 8), out_words = chunk * p.output_len + 1;
   const size_t off_in = total; total += up(in_bytes);
-  const size_t off_out = total; total += up(out_words * 8);
-  // the shift step of a Softmax on the host side: [its input of the chunk][the error word][the shifts]
+  const size_t off_out = total; total += up(out_words * 8 + stat_bytes);
+  // the shift step of a Softmax on the host side: [its input of the chunk][the error word, the status words][the shifts]
+  const size_t sm_mid = up(8 + stat_bytes);
   size_t sm_in = 0, sm_sh = 0;
   for (const InferOp& o : p.ops) if (o.kind == IO_SOFTMAX) { sm_in = std::max(sm_in, up(chunk * p.tensors[(size_t)o.in0].len * 8)); sm_sh = std::max(sm_sh, chunk * p.tensors[(size_t)o.in1].len * 8); }
   char* scratch = nullptr; char* pinned = nullptr;
-  size_t launches[IO_KINDS + 2] = {0}, n_i8 = 0, n_i64 = 0, nchunks = 0, trips = 0;
+  size_t launches[IO_KINDS + 2] = {0}, n_i8 = 0, n_i64 = 0, nchunks = 0, trips = 0, nrefused = 0;
   double trip_ms = 0;
   unsigned err = 0;
   auto cleanup = [&] { (void)hipStreamSynchronize(s); if (scratch) (void)hipFree(scratch); if (pinned) (void)hipHostFree(pinned); scratch = pinned = nullptr; };
   try {
     HIP_CHECK(hipMalloc((void**)&scratch, total));
-    HIP_CHECK(hipHostMalloc((void**)&pinned, std::max(std::max(in_bytes, out_words * 8), sm_in + 256 + sm_sh), hipHostMallocDefault));
+    HIP_CHECK(hipHostMalloc((void**)&pinned, std::max(std::max(in_bytes, out_words * 8 + stat_bytes), sm_in + sm_mid + sm_sh), hipHostMallocDefault));
     auto T64 = [&](int t) { return (int64_t*)(scratch + off64[(size_t)t]); };
     auto T8 = [&](int t) { return q[(size_t)t] ? (int8_t*)(scratch + off8[(size_t)t]) : (int8_t*)nullptr; };
     int64_t* dout = (int64_t*)(scratch + off_out);
     unsigned* derr = (unsigned*)(dout + chunk * p.output_len);
+    unsigned* dstat = checked ? (unsigned*)(dout + out_words) : nullptr;  // (null: the kernels raise the error word)
     auto grid = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
     for (size_t b0 = 0; b0 < ninputs && !err; b0 += chunk, nchunks++) {
       const size_t nb = std::min(chunk, ninputs - b0), nin = nb * p.input_len;
       if (in_q) { int8_t* h = (int8_t*)pinned; const int64_t* src = inputs + b0 * p.input_len; for (size_t i = 0; i < nin; i++) h[i] = (int8_t)src[i]; }
       else memcpy(pinned, inputs + b0 * p.input_len, nin * 8);
       HIP_CHECK(hipMemcpyAsync(scratch + off_in, pinned, nin * (in_q ? 1 : 8), hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemsetAsync(derr, 0, 8, s));
+      HIP_CHECK(hipMemsetAsync(derr, 0, 8 + stat_bytes, s));
       size_t ioff = 0;
       for (int t : p.inputs) {
         const size_t len = p.tensors[(size_t)t].len, n = nb * len;
@@ -302,34 +341,39 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
             k_infer_gemm_i64<<<grid(n), 256, 0, s>>>(T64(o.in0), p.tensors[(size_t)o.in0].len, T64(o.in1), p.tensors[(size_t)o.in1].len, nullptr, T64(o.out), p.tensors[(size_t)o.out].len, nb, o.g);
             n_i64++;
             break;
-          case IO_REQUANT: k_infer_requant<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.out), T8(o.out), n, o.left, o.shift, o.bits, derr); break;
+          case IO_REQUANT: k_infer_requant<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.out), T8(o.out), n, o.left, o.shift, o.bits, derr, dstat, p.tensors[(size_t)o.out].len); break;
           case IO_RELU: k_infer_relu<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.out), T8(o.out), n); break;
           case IO_ADDC: k_infer_addc<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.w), T64(o.out), n, p.tensors[(size_t)o.out].len, o.left, o.right); break;
           case IO_ADD2: k_infer_add2<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.in1), T64(o.out), n, o.left, o.right); break;
-          case IO_EMBED: k_infer_embed<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.w), T64(o.out), n, o.d[0], o.d[1], derr); break;
+          case IO_EMBED: k_infer_embed<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.w), T64(o.out), n, o.d[0], o.d[1], derr, dstat, p.tensors[(size_t)o.out].len); break;
           case IO_MAXPOOL: k_infer_maxpool<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.out), T8(o.out), n, o.d[1], o.d[2]); break;
           case IO_CONV: k_infer_conv<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.w), const64(o.bias), T64(o.out), n, o.d[0], o.d[1], o.d[2], o.d[3], o.d[4], o.d[5], o.d[6]); break;
-          case IO_GELU: k_infer_gelu<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.table), T64(o.out), n, o.left, (int64_t)o.d[0], derr); break;
+          case IO_GELU: k_infer_gelu<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.table), T64(o.out), n, o.left, (int64_t)o.d[0], derr, dstat, p.tensors[(size_t)o.out].len); break;
           case IO_LAYERNORM: {
             const size_t rows = n / o.d[0];
-            k_infer_layernorm<<<grid(rows * 64), 256, 0, s>>>(T64(o.in0), const64(o.w), const64(o.bias), const64(o.table), T64(o.out), rows, o.d[0], (int64_t)o.d[1], o.left, o.shift, derr);
+            k_infer_layernorm<<<grid(rows * 64), 256, 0, s>>>(T64(o.in0), const64(o.w), const64(o.bias), const64(o.table), T64(o.out), rows, o.d[0], (int64_t)o.d[1], o.left, o.shift, derr, dstat, p.tensors[(size_t)o.out].len / o.d[0]);
             break;
           }
           case IO_SOFTMAX: {
             // the shift of every row is made on the host, by the function the host inference calls. The error word comes first: rows that follow
-            // bad data are not read
+            // bad data are not read. Checked mode: the status words take its place — the samples refused so far are skipped, those the range check
+            // refuses here are marked, and the words go back to the device with the shifts
             const auto ts = std::chrono::steady_clock::now();
             const size_t nx = nb * p.tensors[(size_t)o.in0].len, nsh = nb * p.tensors[(size_t)o.in1].len;
             const int64_t* table = const64(o.table);
             HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(pinned + sm_in, derr, 8, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(pinned + sm_in, derr, 8 + nb * (checked ? 4 : 0), hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipMemcpyAsync(pinned, T64(o.in0), nx * 8, hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
             err = *(const unsigned*)(pinned + sm_in);
-            if (!err && !p.shifts(o, (const int64_t*)pinned, nb, (int64_t*)(pinned + sm_in + 256))) err = INFER_ERR_SOFTMAX;
+            if (checked) {
+              p.shifts_checked(o, (const int64_t*)pinned, nb, (int64_t*)(pinned + sm_in + sm_mid), (uint32_t*)(pinned + sm_in + 8));
+              HIP_CHECK(hipMemcpyAsync(dstat, pinned + sm_in + 8, nb * 4, hipMemcpyHostToDevice, s));
+            } else if (!err && !p.shifts(o, (const int64_t*)pinned, nb, (int64_t*)(pinned + sm_in + sm_mid))) err = INFER_ERR_SOFTMAX;
             if (!err) {
-              HIP_CHECK(hipMemcpyAsync(T64(o.in1), pinned + sm_in + 256, nsh * 8, hipMemcpyHostToDevice, s));
-              k_infer_softmax<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.in1), table, T64(o.out), n, o.d[1], o.d[2], o.left, -(((o.right >> 16) + 1) << 16), o.bits, (unsigned)o.d[3], (unsigned)o.d[4], derr);
+              HIP_CHECK(hipMemcpyAsync(T64(o.in1), pinned + sm_in + sm_mid, nsh * 8, hipMemcpyHostToDevice, s));
+              k_infer_softmax<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.in1), table, T64(o.out), n, o.d[1], o.d[2], o.left, -(((o.right >> 16) + 1) << 16), o.bits, (unsigned)o.d[3], (unsigned)o.d[4], derr,
+                                                      dstat, p.tensors[(size_t)o.out].len);
             }
             trips++; trip_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
             break;
@@ -345,21 +389,30 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
         ooff += len; launches[IO_KINDS + 1]++;
       }
       HIP_CHECK(hipGetLastError());
-      // the outputs and the error word behind them: one copy (a partial last chunk: the word is fetched on its own)
-      const size_t nout = nb * p.output_len;
-      if (nb == chunk) HIP_CHECK(hipMemcpyAsync(pinned, dout, (nout + 1) * 8, hipMemcpyDeviceToHost, s));
-      else { HIP_CHECK(hipMemcpyAsync(pinned, dout, nout * 8, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipMemcpyAsync(pinned + nout * 8, derr, 8, hipMemcpyDeviceToHost, s)); }
+      // the outputs, the error word behind them and (checked mode) the status words behind that: one copy (a partial last chunk: the words
+      // are fetched on their own)
+      const size_t nout = nb * p.output_len, tail = 8 + nb * (checked ? 4 : 0);
+      if (nb == chunk) HIP_CHECK(hipMemcpyAsync(pinned, dout, nout * 8 + tail, hipMemcpyDeviceToHost, s));
+      else { HIP_CHECK(hipMemcpyAsync(pinned, dout, nout * 8, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipMemcpyAsync(pinned + nout * 8, derr, tail, hipMemcpyDeviceToHost, s)); }
       HIP_CHECK(hipStreamSynchronize(s));
-      err = *(const unsigned*)(pinned + nout * 8);
+      err = *(const unsigned*)(pinned + nout * 8);  // (checked mode: nothing raises it)
+      if (checked) {  // refused samples: the reason, and zeros for whatever the later kernels made of them
+        const uint32_t* hs = (const uint32_t*)(pinned + nout * 8 + 8);
+        for (size_t i = 0; i < nb; i++) {
+          reasons[b0 + i] = hs[i];
+          if (hs[i]) { memset(outputs + (b0 + i) * out_stride, 0, p.output_len * 8); nrefused++; }
+          else memcpy(outputs + (b0 + i) * out_stride, pinned + i * p.output_len * 8, p.output_len * 8);
+        }
+      } else
       if (!err) for (size_t i = 0; i < nb; i++) memcpy(outputs + (b0 + i) * out_stride, pinned + i * p.output_len * 8, p.output_len * 8);
     }
   } catch (...) { cleanup(); throw; }
   cleanup();
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (wall_ms) *wall_ms = ms;
-  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu conv %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms\n",
+  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu conv %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s\n",
                    n_i8, n_i64, launches[IO_CONV], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], trips, trip_ms,
-                   ninputs, nchunks, chunk, (double)total / 1048576.0, in_q ? "int8" : "int64", ms);
+                   ninputs, nchunks, chunk, (double)total / 1048576.0, in_q ? "int8" : "int64", ms, checked ? ("; checked, refused " + std::to_string(nrefused)).c_str() : "");
   DP_REQUIRE(!(err & INFER_ERR_REQUANT), DP_ERR_ARG, "requant: value exceeds intermediate bit size");
   DP_REQUIRE(!(err & INFER_ERR_TOKEN), DP_ERR_ARG, "embeddings: token outside the vocabulary");
   DP_REQUIRE(!(err & INFER_ERR_GELU), DP_ERR_ARG, "gelu: input out of range");

@@ -22,9 +22,20 @@
  * dp_model_infer_host does for that input); the model stays usable. The device error word is read before the host computes any shift, so no
  * row that follows bad data reaches expf. Flag bits other than DP_INFER_ALL_KINDS: DP_ERR_ARG.
  *
+ * dp_model_infer_checked refuses such data input by input instead: the call returns DP_OK, every chunk of the batch is processed, and
+ * reasons[i] says whether input i was inferred (DP_INFER_OK: its row holds the integers of dp_model_infer_host) or which kind of node refused
+ * it first, in node order (DP_INFER_BAD_*: dp_model_infer_host returns DP_ERR_ARG for that input with the message of that class; its row is
+ * zeros). On the device every sample of a chunk has a status word that only the first refusal writes; a refused sample's values travel on
+ * through the later kernels, which stay inside their tables and buffers on any data, and the host's Softmax shift step skips refused samples
+ * (zero shifts: nothing of theirs reaches expf) and range-checks the others one by one. What is wrong with the model or the call — bad
+ * pointers, a wrong input length, an output buffer too small, unknown flag bits, a kind refused under the flag word given — stays an error of
+ * the call, with the codes and messages of dp_model_infer_ex. A batch can so be screened before it is proved (Python:
+ * Prover.prove_batch_screened): dp_model_prove_batch discards every proof of a batch in which the host inference of one input throws.
+ *
  * Knobs (environment): DP_INFER_SCRATCH_MB (activation scratch of one chunk of the batch, default 1024), DP_INFER_NO_MFMA=1 (64-bit
  * products everywhere), DP_INFER_LOG=1 (one `[dp infer]` line per call on stderr: launches per kernel, chunks, wall time; gelu / layernorm / softmax launches,
- * shift_trips = round trips of the Softmax shift step and shift_ms = the milliseconds spent in them).
+ * shift_trips = round trips of the Softmax shift step and shift_ms = the milliseconds spent in them; a checked call appends
+ * `; checked, refused N`).
  */
 #ifndef DEEP_PROVE_HIP_INFER_H
 #define DEEP_PROVE_HIP_INFER_H
@@ -44,6 +55,19 @@ int32_t dp_model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, size_
  * model is kept per flag word. */
 int32_t dp_model_infer_ex(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags,
                           int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms);
+
+/* The status of one input of dp_model_infer_checked: inferred, or the class of the first node (in node order) at which the host refuses it. */
+#define DP_INFER_OK            0u
+#define DP_INFER_BAD_REQUANT   1u   /* host: "requant: ..." */
+#define DP_INFER_BAD_TOKEN     2u   /* host: "embeddings: token outside the vocabulary" */
+#define DP_INFER_BAD_GELU      3u   /* host: "gelu: ..." */
+#define DP_INFER_BAD_LAYERNORM 4u   /* either "layernorm: ..." message */
+#define DP_INFER_BAD_SOFTMAX   5u   /* host: "softmax: ..." */
+/* dp_model_infer_ex (the same flags, the same flattened model and device constants) with a status per input instead of DP_ERR_ARG for the whole
+ * batch. reasons: ninputs words; row i of outputs is zero-filled when reasons[i] != DP_INFER_OK; *nrefused (nullable) = the number of such rows. */
+int32_t dp_model_infer_checked(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags,
+                               int64_t* outputs, size_t noutput_cap, size_t* noutput,
+                               uint32_t* reasons /* ninputs */, size_t* nrefused /* nullable */, double* wall_ms /* nullable */);
 
 #ifdef __cplusplus
 }

@@ -133,4 +133,4 @@ unsafe impl Sync for Words {}
 
 /// `include/deep_prove_hip_infer.h`: batched quantised inference on the device (`dp_model_infer`), declared in a module of its own.
 pub mod infer;
-pub use infer::{dp_model_infer, dp_model_infer_ex, DP_INFER_ALL_KINDS};
+pub use infer::{dp_model_infer, dp_model_infer_checked, dp_model_infer_ex, DP_INFER_ALL_KINDS};
