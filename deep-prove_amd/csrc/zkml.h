@@ -461,13 +461,15 @@ DP_HOST_CLONES inline int32_t dot_i16(const int16_t* a, const int16_t* b, size_t
 DP_HOST_CLONES inline void axpy_i16(int32_t* acc, int32_t x, const int16_t* w, size_t n) { for (size_t j = 0; j < n; j++) acc[j] += x * (int32_t)w[j]; }
 // the weights of a Dense / MatMul layer once more as int16 when they all fit (quantised models: |w| <= 127): the inference that precedes
 // every proof then streams a quarter of the bytes and its multiply-adds vectorise in 32-bit lanes
+// |v| without the overflow of -INT64_MIN (2^63 as an unsigned value: beyond every bound it is compared with)
+inline uint64_t abs_u64(int64_t v) { return v < 0 ? 0 - (uint64_t)v : (uint64_t)v; }
 inline void prepare_fast_inference(LayerSpec& l) {
   if (l.kind != L_DENSE && l.kind != L_MATMUL && l.kind != L_QKV) return;
-  int64_t wm = 0; for (int64_t v : l.weights) wm = std::max(wm, v < 0 ? -v : v);
+  uint64_t wm = 0; for (int64_t v : l.weights) wm = std::max(wm, abs_u64(v));
   if (wm > 32767) return;
   auto w16 = std::make_shared<std::vector<int16_t>>(l.weights.size());
   for (size_t j = 0; j < l.weights.size(); j++) (*w16)[j] = (int16_t)l.weights[j];
-  l.w16 = w16; l.w16_max = wm;
+  l.w16 = w16; l.w16_max = (int64_t)wm;
 }
 // [s][k] activations (as int16) times a constant [k][n] matrix (or its transpose [n][k]) kept as int16, exact in int32 (the caller has checked the bound), + bias:
 // eight rows of the activation share every pass over the matrix — a row of W (2 KB at n = 1024) is read once per eight tokens
@@ -550,7 +552,7 @@ inline Trace run_model(const ModelSpec& m, const std::vector<int64_t>& input) {
     } else if (l.kind == L_QKV) {  // QKV::evaluate (qkv.rs:275-340, no cache)
       const size_t k = l.nrows, n = l.ncols;
       DP_REQUIRE(k && cur.size() % k == 0 && l.weights.size() == 3 * k * n && l.bias.size() == 3 * n, DP_ERR_SHAPE, "qkv: shapes");
-      int64_t xmax = 0; for (int64_t v : cur) xmax = std::max(xmax, v < 0 ? -v : v);
+      uint64_t xmax = 0; for (int64_t v : cur) xmax = std::max(xmax, abs_u64(v));
       const bool fast = l.w16 && xmax <= 32767 && (double)xmax * (double)l.w16_max * (double)k < 2.0e9;  // exact in int32: the same integers as matmul_i64 gives
       std::vector<int16_t> x16; if (fast) { x16.resize(cur.size()); for (size_t j = 0; j < cur.size(); j++) x16[j] = (int16_t)cur[j]; }
       for (size_t w = 0; w < 3; w++) {
@@ -572,7 +574,7 @@ inline Trace run_model(const ModelSpec& m, const std::vector<int64_t>& input) {
     if (l.kind == L_DENSE) {
       DP_REQUIRE(cur.size() == l.ncols, DP_ERR_SHAPE, "dense input size mismatch");
       o.resize(l.nrows);
-      int64_t xmax = 0; for (int64_t v : cur) xmax = std::max(xmax, v < 0 ? -v : v);
+      uint64_t xmax = 0; for (int64_t v : cur) xmax = std::max(xmax, abs_u64(v));
       if (l.w16 && xmax <= 32767 && (double)xmax * (double)l.w16_max * (double)l.ncols < 2.0e9) {  // exact in int32: same integers as below
         std::vector<int16_t> x16(cur.size()); for (size_t j = 0; j < cur.size(); j++) x16[j] = (int16_t)cur[j];
         const int16_t* xp = x16.data();
@@ -584,7 +586,7 @@ inline Trace run_model(const ModelSpec& m, const std::vector<int64_t>& input) {
       DP_REQUIRE(k && cur.size() % k == 0, DP_ERR_SHAPE, "matmul input size mismatch");
       const size_t s_ = cur.size() / k;
       o.assign(s_ * n, 0);
-      int64_t xmax = 0; for (int64_t v : cur) xmax = std::max(xmax, v < 0 ? -v : v);
+      uint64_t xmax = 0; for (int64_t v : cur) xmax = std::max(xmax, abs_u64(v));
       if (l.w16 && xmax <= 32767 && (double)xmax * (double)l.w16_max * (double)k < 2.0e9) {  // exact in int32: the same integers as the int64 loops below
         std::vector<int16_t> x16(cur.size()); for (size_t j = 0; j < cur.size(); j++) x16[j] = (int16_t)cur[j];
         matmul_w16(x16.data(), s_, k, n, l.w16->data(), l.mm_transpose, l.bias.empty() ? nullptr : l.bias.data(), o.data());
@@ -612,7 +614,7 @@ inline Trace run_model(const ModelSpec& m, const std::vector<int64_t>& input) {
     } else if (l.kind == L_REQUANT) {
       unsigned sh = l.shift();
       for (int64_t v : cur) {
-        DP_REQUIRE((v < 0 ? -v : v) <= (int64_t(1) << l.intermediate_bit_size), DP_ERR_ARG, "requant: value exceeds intermediate bit size");
+        DP_REQUIRE(abs_u64(v) <= (uint64_t(1) << l.intermediate_bit_size), DP_ERR_ARG, "requant: value exceeds intermediate bit size");
         o.push_back(q_clamp((v * l.fixed_point_multiplier + (int64_t(1) << (sh - 1))) >> sh));
       }
     } else if (l.kind == L_RELU) for (int64_t v : cur) o.push_back(q_relu(v));
