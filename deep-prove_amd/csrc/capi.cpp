@@ -1374,11 +1374,11 @@ int32_t dp_model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, size_
   return dp_model_infer_ex(m, inputs, ninputs, ninput, 0, outputs, noutput_cap, noutput, wall_ms);
 }
 static_assert(DP_INFER_OK == INFER_OK && DP_INFER_BAD_REQUANT == INFER_BAD_REQUANT && DP_INFER_BAD_TOKEN == INFER_BAD_TOKEN && DP_INFER_BAD_GELU == INFER_BAD_GELU &&
-              DP_INFER_BAD_LAYERNORM == INFER_BAD_LAYERNORM && DP_INFER_BAD_SOFTMAX == INFER_BAD_SOFTMAX && DP_INFER_ALL_KINDS == INFER_ALL_KINDS, "deep_prove_hip_infer.h and infer.h");
+              DP_INFER_BAD_LAYERNORM == INFER_BAD_LAYERNORM && DP_INFER_BAD_SOFTMAX == INFER_BAD_SOFTMAX && INFER_BAD_LAYERNORM_TABLE > DP_INFER_BAD_SOFTMAX && DP_INFER_ALL_KINDS == INFER_ALL_KINDS, "deep_prove_hip_infer.h and infer.h");
 // reasons null: dp_model_infer_ex. Not null: dp_model_infer_checked (the same program and device constants for the same flag word)
-static int32_t model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, size_t* nrefused, double* wall_ms, bool checked) {
+static int32_t model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, size_t* nrefused, double* wall_ms) {
   return guard([&] {
-    DP_REQUIRE(m && inputs && outputs && noutput && (!checked || reasons), DP_ERR_ARG, "bad arguments");
+    DP_REQUIRE(m && inputs && outputs && noutput, DP_ERR_ARG, "bad arguments");
     DP_REQUIRE(!(flags & ~(uint32_t)DP_INFER_ALL_KINDS), DP_ERR_ARG, "dp_model_infer_ex: unknown flag bits");
     const ModelSpec& spec = m->zk->model;
     DP_REQUIRE(ninput == spec.input_len, DP_ERR_SHAPE, "input length mismatch");
@@ -1396,10 +1396,11 @@ static int32_t model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, s
   });
 }
 int32_t dp_model_infer_ex(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms) {
-  return model_infer(m, inputs, ninputs, ninput, flags, outputs, noutput_cap, noutput, nullptr, nullptr, wall_ms, false);
+  return model_infer(m, inputs, ninputs, ninput, flags, outputs, noutput_cap, noutput, nullptr, nullptr, wall_ms);
 }
 int32_t dp_model_infer_checked(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, size_t* nrefused, double* wall_ms) {
-  return model_infer(m, inputs, ninputs, ninput, flags, outputs, noutput_cap, noutput, reasons, nrefused, wall_ms, true);
+  if (!reasons) return guard([] { throw DpError(DP_ERR_ARG, "bad arguments"); });
+  return model_infer(m, inputs, ninputs, ninput, flags, outputs, noutput_cap, noutput, reasons, nrefused, wall_ms);
 }
 int32_t dp_host_poseidon2(uint64_t state[8], int32_t force_scalar, int32_t* vectorised) {
   return guard([&] {

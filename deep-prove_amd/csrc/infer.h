@@ -9,14 +9,13 @@
 // computation that depends on the data, the shift of a Softmax row, stays on the host: at an IO_SOFTMAX hip_infer_run downloads the input of
 // the chunk, calls InferProgram::shifts (infer_softmax_shifts below: softmax_row_shift of zkml.h, the function softmax_op calls) and uploads
 // one shift per row. An Mha node is three ops: the product Q K^T, the Softmax, the product with V.
-// Checked mode (dp_model_infer_checked: hip_infer_run with `reasons`) refuses inputs one by one instead of the call: one status word per sample
-// of the chunk holds the class (INFER_BAD_*) of the first op that refused it; the shift step works sample by sample (InferProgram::shifts_checked,
-// infer_softmax_shifts_checked below) and never reads the rows of a sample that is already refused. Program and constants are those of the
-// plain call with the same flag word.
+// Data the host would refuse: one status word per sample of the chunk holds the class (INFER_BAD_*) of the first op that refused the sample; the
+// shift step works sample by sample and never reads the rows of a sample that is already refused. The two kinds of call differ only in what
+// hip_infer_run does with the words: with `reasons` (dp_model_infer_checked) it refuses inputs one by one, without (dp_model_infer_ex) the
+// first chunk that holds a refused sample ends the call with the host's message for its class. Program and constants are the same for both.
 #pragma once
 #include "dev.h"
 #include <algorithm>
-#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <functional>
@@ -36,8 +35,10 @@ struct InferConst {
   const int64_t* data() const { return own.empty() ? h64 : own.data(); }
 };
 constexpr uint32_t INFER_ALL_KINDS = 1;  // (DP_INFER_ALL_KINDS of the public header)
-// the status of one input in checked mode (DP_INFER_OK, DP_INFER_BAD_* of the public header): which kind of node refused it first
+// the status of one input (DP_INFER_OK, DP_INFER_BAD_* of the public header): which kind of node refused it first
 constexpr uint32_t INFER_OK = 0, INFER_BAD_REQUANT = 1, INFER_BAD_TOKEN = 2, INFER_BAD_GELU = 3, INFER_BAD_LAYERNORM = 4, INFER_BAD_SOFTMAX = 5;
+// internal only: a LayerNorm's inverse square root input leaves its table (the host has a message of its own for it; INFER_BAD_LAYERNORM in `reasons`)
+constexpr uint32_t INFER_BAD_LAYERNORM_TABLE = 6;
 enum InferOpKind { IO_GEMM = 0, IO_GEMM2, IO_REQUANT, IO_RELU, IO_ADDC, IO_ADD2, IO_EMBED, IO_MAXPOOL, IO_CONV, IO_GELU, IO_LAYERNORM, IO_SOFTMAX, IO_KINDS };
 // out[b][c*sOc + r*sOr + n*sOn] = sum_m A[b][c*sAc + r*sAr + m*sAm] * B[(B a tensor: b)][c*sBc + m*sBm + n*sBn] (+ bias[n])
 struct InferGemmShape { size_t C = 1, R = 0, K = 0, N = 0; size_t sAc = 0, sAr = 0, sAm = 0, sBc = 0, sBm = 0, sBn = 0, sOc = 0, sOr = 0, sOn = 0; };
@@ -59,18 +60,16 @@ struct InferProgram {
   std::vector<int> inputs, outputs;  // tensor ids of the model's input / output tensors, in the order they are concatenated
   std::vector<InferConst> consts;
   std::vector<InferOp> ops;
-  // the shift step of an IO_SOFTMAX: x = its input for nb samples; shifts: nb x C * R words. False: an input beyond 2^24 (no shift is made of such a sample)
-  std::function<bool(const InferOp& o, const int64_t* x, size_t nb, int64_t* shifts)> shifts;
-  // the same step sample by sample (checked mode). status: nb words; a sample whose word is set is not read and gets zero shifts, a sample with an
-  // input beyond 2^24 gets INFER_BAD_SOFTMAX and zero shifts
-  std::function<void(const InferOp& o, const int64_t* x, size_t nb, int64_t* shifts, uint32_t* status)> shifts_checked;
+  // the shift step of an IO_SOFTMAX: x = its input for nb samples; shifts: nb x C * R words; status: nb words. A sample whose word is set is not
+  // read and gets zero shifts, a sample with an input beyond 2^24 gets INFER_BAD_SOFTMAX and zero shifts
+  std::function<void(const InferOp& o, const int64_t* x, size_t nb, int64_t* shifts, uint32_t* status)> shifts;
 };
 struct InferDeviceState;  // the constants on the device (made at the first call, freed with the model)
 InferDeviceState* hip_infer_state_new(int device);
 void hip_infer_state_free(InferDeviceState* s);
 // inputs: ninputs x p.input_len words; outputs: ninputs x out_stride words (the first p.output_len of each row are written). Throws DpError.
 // reasons (ninputs words) not null: checked mode — bad data refuses its input (reasons[i] = INFER_BAD_*, the output row zeros), not the call, and
-// every chunk is processed.
+// every chunk is processed. Null: the first chunk with a refused sample ends the call (DP_ERR_ARG, the host's message), none of its rows is written.
 void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* inputs, size_t ninputs, int64_t* outputs, size_t out_stride, double* wall_ms, uint32_t* reasons = nullptr);
 
 #ifdef DP_INFER_PLANNER  // (capi.cpp, after zkml.h)
@@ -78,34 +77,11 @@ inline const char* infer_kind_name(int k) {
   static const char* names[] = {"Dense", "Requant", "ReLU", "Conv", "MaxPool", "Flatten", "MatMul", "Add", "Embeddings", "Positional", "MatMul2", "Add2", "ConcatMatMul", "QKV", "LayerNorm", "Softmax", "Mha", "GELU"};
   return k >= 0 && k < 18 ? names[k] : "unknown";
 }
-// the shifts of every Softmax row of nb samples over at most DP_HOST_THREADS threads (never more than 16); every row is range checked before
-// softmax_row_shift sees it, as softmax_op does
-inline bool infer_softmax_shifts(const LayerSpec& sm, const int64_t* x, size_t nb, int64_t* shifts) {
-  const size_t C = sm.sm_shape[0], R = sm.sm_shape[1], K = sm.sm_shape[2], rows = nb * C * R;
-  const char* te = getenv("DP_HOST_THREADS");
-  size_t nth = te ? (size_t)std::max(1, atoi(te)) : (size_t)std::max(1.0, host_cpu_budget() - 2.0);
-  nth = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(nth, 16), rows / 256));
-  std::atomic<bool> ok(true);
-  auto part = [&](size_t t) {
-    for (size_t i = rows * t / nth, e = rows * (t + 1) / nth; i < e && ok.load(std::memory_order_relaxed); i++) {
-      const int64_t* row = x + i * K;
-      bool in = true;
-      for (size_t j = 0; j < K; j++) in = in && row[j] >= -(int64_t(1) << 24) && row[j] <= (int64_t(1) << 24);
-      if (!in) { ok = false; return; }
-      shifts[i] = softmax_row_shift(sm, row, i % R + 1);
-    }
-  };
-  std::vector<std::thread> th;
-  for (size_t t = 1; t < nth; t++) th.emplace_back(part, t);
-  part(0);
-  for (std::thread& t : th) t.join();
-  return ok;
-}
-// the same step sample by sample (checked mode), on as many threads. A sample whose status word is set was refused by an earlier op: its rows
-// hold whatever the later kernels made of it and are NOT read (no value of theirs reaches expf, logf or the conversion to an integer); it gets
-// zero shifts. Every other sample is range checked as a whole before its first shift is made — softmax_op's order — and gets INFER_BAD_SOFTMAX
-// and zero shifts when an element lies beyond 2^24
-inline void infer_softmax_shifts_checked(const LayerSpec& sm, const int64_t* x, size_t nb, int64_t* shifts, uint32_t* status) {
+// the shifts of every Softmax row of nb samples, sample by sample over at most DP_HOST_THREADS threads (never more than 16). A sample whose
+// status word is set (any class) was refused by an earlier op: its rows hold whatever the later kernels made of it and are NOT read (no value of
+// theirs reaches expf, logf or the conversion to an integer); it gets zero shifts and keeps its word. Every other sample is range checked as a
+// whole before its first shift is made — softmax_op's order — and gets INFER_BAD_SOFTMAX and zero shifts when an element lies beyond 2^24
+inline void infer_softmax_shifts(const LayerSpec& sm, const int64_t* x, size_t nb, int64_t* shifts, uint32_t* status) {
   const size_t C = sm.sm_shape[0], R = sm.sm_shape[1], K = sm.sm_shape[2], rows = C * R;
   const char* te = getenv("DP_HOST_THREADS");
   size_t nth = te ? (size_t)std::max(1, atoi(te)) : (size_t)std::max(1.0, host_cpu_budget() - 2.0);
@@ -276,13 +252,9 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
   }
   for (const Edge& e : output_edges(m)) p.outputs.push_back(tensor_of(e));
   // (m is the model of the dp_model that keeps this program: it outlives it)
-  p.shifts = [&m](const InferOp& o, const int64_t* x, size_t nb, int64_t* shifts) {
+  p.shifts = [&m](const InferOp& o, const int64_t* x, size_t nb, int64_t* shifts, uint32_t* status) {
     const LayerSpec& l = m.layers[(size_t)o.node];
-    return infer_softmax_shifts(l.kind == L_MHA ? mha_softmax_spec(l) : l, x, nb, shifts);
-  };
-  p.shifts_checked = [&m](const InferOp& o, const int64_t* x, size_t nb, int64_t* shifts, uint32_t* status) {
-    const LayerSpec& l = m.layers[(size_t)o.node];
-    infer_softmax_shifts_checked(l.kind == L_MHA ? mha_softmax_spec(l) : l, x, nb, shifts, status);
+    infer_softmax_shifts(l.kind == L_MHA ? mha_softmax_spec(l) : l, x, nb, shifts, status);
   };
   return p;
 }

@@ -1,29 +1,28 @@
 // Kernels and the batch runner of dp_model_infer (infer.h). Included by hip_dev.hip after HipDev; not part of kernels.inc (the SIMT-emulator
 // build of tests/ cuts its kernels from there). Activations are [batch][tensor] int64, with an int8 copy next to every tensor whose values are
 // known to lie within -128..127 (what a Requant writes, and what ReLU / MaxPool make of it): the int8 copies are the operands of k_infer_gemm_i8.
-// Bad data (a Requant input beyond its bit size, a token outside the vocabulary) raises bits of a device error word with a vector atomic; the
-// host reads it with the outputs. Every launch is finite; nothing here waits for the host. A Softmax (IO_SOFTMAX) splits the chunk's stream in
-// two: the host reads the error word and the Softmax input, computes one shift per row (InferProgram::shifts) and uploads them.
-// Checked mode (dp_model_infer_checked: `status` not null in the five kernels that can refuse data) keeps one status word per sample of the
-// chunk instead: the class (INFER_BAD_* of infer.h) of the first op that refused the sample. Ops run in stream order and the word only ever
-// goes from zero to a class (compare-and-swap), so whatever later ops make of a refused sample's values cannot change it. Those values travel
-// on; the guards that keep every kernel inside its tables and buffers on such data are named at each kernel.
+// Bad data (a Requant input beyond its bit size, a token outside the vocabulary, ...) refuses its sample: the chunk has one status word per
+// sample, which the five kernels that can refuse data set with a vector atomic to the class (INFER_BAD_* of infer.h) of the first op that refused
+// the sample; the host reads the words with the outputs. Ops run in stream order and the word only ever goes from zero to a class
+// (compare-and-swap), so whatever later ops make of a refused sample's values cannot change it. Those values travel on; the guards that keep
+// every kernel inside its tables and buffers on such data are named at each kernel. What a refused sample means for the call (dp_model_infer_ex:
+// the call fails; dp_model_infer_checked: the input is refused) is decided on the host, in hip_infer_run. Every launch is finite; nothing here
+// waits for the host. A Softmax (IO_SOFTMAX) splits the chunk's stream in two: the host reads the status words and the Softmax input, computes
+// one shift per row of every sample not refused so far (InferProgram::shifts) and uploads words and shifts.
 
 typedef int infer_v4i __attribute__((ext_vector_type(4)));
 typedef int infer_v16i __attribute__((ext_vector_type(16)));
 constexpr int IG_TM = 64, IG_TN = 64, IG_TK = 64, IG_LD = IG_TK + 16;  // tile of a workgroup (4 waves, 32 x 32 each); LDS row pitch in bytes
-constexpr unsigned INFER_ERR_REQUANT = 1, INFER_ERR_TOKEN = 2, INFER_ERR_GELU = 4, INFER_ERR_LN_INPUT = 8, INFER_ERR_LN_TABLE = 16, INFER_ERR_SOFTMAX = 32;
 
-// Checked mode: sample `s` is refused with class `cls` unless an earlier op (or an earlier wave of this one: same class) refused it. The plain
+// Sample `s` is refused with class `cls` unless an earlier op (or an earlier wave of this one: same class) refused it. The plain
 // load keeps the atomics of a sample that is bad everywhere to the few waves that run before the first of them lands
 __device__ __forceinline__ void infer_refuse(unsigned* status, size_t s, unsigned cls) {
   if (__hip_atomic_load(status + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) atomicCAS(status + s, 0u, cls);
 }
 // What an element-wise kernel does with `bad` (element i of a tensor of `per` words per sample; every lane of the wave that has an element calls
-// it, in converged control flow). Plain mode: the bit of the chunk's error word. Checked mode: one wave-wide vote — nothing more on good data —
-// and then one atomic per run of bad lanes and sample, from the first lane of the run (a wave of 64 consecutive elements can straddle samples)
-__device__ __forceinline__ void infer_flag(bool bad, size_t i, size_t per, unsigned* status, unsigned cls, unsigned* err, unsigned bit) {
-  if (!status) { if (bad) atomicOr(err, bit); return; }
+// it, in converged control flow): one wave-wide vote — nothing more on good data — and then one atomic per run of bad lanes and sample, from
+// the first lane of the run (a wave of 64 consecutive elements can straddle samples)
+__device__ __forceinline__ void infer_flag(bool bad, size_t i, size_t per, unsigned* status, unsigned cls) {
   const unsigned long long m = __ballot(bad);
   if (!m) return;
   const unsigned lane = threadIdx.x & 63;
@@ -93,16 +92,15 @@ __global__ __launch_bounds__(256) void k_infer_gemm_i64(const int64_t* __restric
   if (bias) acc += (uint64_t)bias[n];
   O[b * lenO + c * g.sOc + r * g.sOr + n * g.sOn] = (int64_t)acc;
 }
-// Requant::apply: (v * mult + 2^(sh-1)) >> sh clamped to +-127; |v| > 2^bits raises the error word (the host refuses the whole call, as run_model does)
-// or, in checked mode, refuses the sample (per = words per sample). A refused sample's output is clamped like any other: its int8 copy stays a
-// valid operand of k_infer_gemm_i8
-__global__ __launch_bounds__(256) void k_infer_requant(const int64_t* __restrict__ x, int64_t* __restrict__ o, int8_t* __restrict__ o8, size_t n, int64_t mult, unsigned sh, unsigned bits, unsigned* err,
+// Requant::apply: (v * mult + 2^(sh-1)) >> sh clamped to +-127; |v| > 2^bits refuses the sample, as run_model refuses the input (per = words per
+// sample). A refused sample's output is clamped like any other: its int8 copy stays a valid operand of k_infer_gemm_i8
+__global__ __launch_bounds__(256) void k_infer_requant(const int64_t* __restrict__ x, int64_t* __restrict__ o, int8_t* __restrict__ o8, size_t n, int64_t mult, unsigned sh, unsigned bits,
                                                        unsigned* status, size_t per) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t v = x[i];
   const uint64_t mag = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
-  infer_flag(mag > (uint64_t(1) << bits), i, per, status, INFER_BAD_REQUANT, err, INFER_ERR_REQUANT);
+  infer_flag(mag > (uint64_t(1) << bits), i, per, status, INFER_BAD_REQUANT);
   int64_t y = (int64_t)((uint64_t)v * (uint64_t)mult + (uint64_t(1) << (sh - 1))) >> sh;
   y = y < -127 ? -127 : y > 127 ? 127 : y;
   o[i] = y;
@@ -124,15 +122,15 @@ __global__ __launch_bounds__(256) void k_infer_add2(const int64_t* __restrict__ 
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) o[i] = (int64_t)((uint64_t)left * (uint64_t)x[i] + (uint64_t)right * (uint64_t)y[i]);
 }
-// Embeddings: row tok[t] of the [vocab][emb] table for every token; a token outside the vocabulary raises the error word, or refuses the sample
-// in checked mode (per = output words per sample), and reads row 0: the table is never read outside its rows, whatever the token
-__global__ __launch_bounds__(256) void k_infer_embed(const int64_t* __restrict__ tok, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n, size_t vocab, size_t emb, unsigned* err,
+// Embeddings: row tok[t] of the [vocab][emb] table for every token; a token outside the vocabulary refuses the sample (per = output words per
+// sample) and reads row 0: the table is never read outside its rows, whatever the token
+__global__ __launch_bounds__(256) void k_infer_embed(const int64_t* __restrict__ tok, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n, size_t vocab, size_t emb,
                                                      unsigned* status, size_t per) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int64_t t = tok[i / emb];
   const bool bad = t < 0 || (uint64_t)t >= vocab;
-  infer_flag(bad, i, per, status, INFER_BAD_TOKEN, err, INFER_ERR_TOKEN);
+  infer_flag(bad, i, per, status, INFER_BAD_TOKEN);
   if (bad) t = 0;
   o[i] = table[(size_t)t * emb + i % emb];
 }
@@ -163,16 +161,15 @@ __global__ __launch_bounds__(256) void k_infer_conv(const int64_t* __restrict__ 
   o[i] = (int64_t)acc;
 }
 // Activation::Gelu (gelu_op): table[v * mult + max], the table's rows being -max .. max - 1. |v| > 2^20 or a scaled value outside the table
-// raises the error word (checked mode: refuses the sample, per = words per sample) and nothing is read: the same test guards the table against
-// the values of a sample refused earlier
-__global__ __launch_bounds__(256) void k_infer_gelu(const int64_t* __restrict__ x, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n, int64_t mult, int64_t mx, unsigned* err,
+// refuses the sample (per = words per sample) and nothing is read: the same test guards the table against the values of a sample refused earlier
+__global__ __launch_bounds__(256) void k_infer_gelu(const int64_t* __restrict__ x, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n, int64_t mult, int64_t mx,
                                                     unsigned* status, size_t per) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t v = x[i], lim = int64_t(1) << 20;
   const int64_t scaled = (int64_t)((uint64_t)v * (uint64_t)mult);  // (|v| <= 2^20 and mult <= 2^12 once the first check holds)
   const bool bad = v < -lim || v > lim || scaled < -mx || scaled >= mx;
-  infer_flag(bad, i, per, status, INFER_BAD_GELU, err, INFER_ERR_GELU);
+  infer_flag(bad, i, per, status, INFER_BAD_GELU);
   if (bad) { o[i] = 0; return; }
   o[i] = table[scaled + mx];
 }
@@ -183,11 +180,12 @@ __device__ __forceinline__ uint64_t infer_wave_sum(uint64_t v) {
 }
 // LayerNorm::evaluate (layernorm_op): one wave per row of fd elements (a power of two; lanes beyond a short row add zeros). 64-bit wrap-around
 // arithmetic as on the host: full = N mult sum(x^2) - mult sum(x)^2, in = full >> rcb (arithmetic), out = gamma (N x - sum) lut[in + 2^14] + beta.
-// |x| > 2^20 anywhere in the row, or `in` outside the table, raises the error word and the row is written as zeros (the table is not read: the
-// test on `in` is the guard for the rows of a sample refused earlier, too). Checked mode: lane 0 refuses the sample of the row (per = rows per
-// sample; a wave never straddles samples here, the vote is the __any below)
+// |x| > 2^20 anywhere in the row (INFER_BAD_LAYERNORM), or else `in` outside the table (INFER_BAD_LAYERNORM_TABLE: the host has a message of its
+// own for it), refuses the sample and the row is written as zeros (the table is not read: the test on `in` is the guard for the rows of a
+// sample refused earlier, too). Lane 0 refuses the sample of the row (per = rows per sample; a wave never straddles samples here, the vote is
+// the __any below); where rows of one sample disagree the input class stands, whichever wave came first
 __global__ __launch_bounds__(256) void k_infer_layernorm(const int64_t* __restrict__ x, const int64_t* __restrict__ gamma, const int64_t* __restrict__ beta, const int64_t* __restrict__ lut,
-                                                         int64_t* __restrict__ o, size_t rows, size_t fd, int64_t nn, int64_t mult, unsigned rcb, unsigned* err, unsigned* status, size_t per) {
+                                                         int64_t* __restrict__ o, size_t rows, size_t fd, int64_t nn, int64_t mult, unsigned rcb, unsigned* status, size_t per) {
   const int lane = threadIdx.x & 63;
   const size_t row = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;  // (the whole wave)
@@ -196,12 +194,12 @@ __global__ __launch_bounds__(256) void k_infer_layernorm(const int64_t* __restri
   uint64_t sq = 0, sum = 0; bool bad = false;
   for (size_t i = lane; i < fd; i += 64) { const int64_t v = xr[i]; bad = bad || v < -lim || v > lim; sq += (uint64_t)v * (uint64_t)v; sum += (uint64_t)v; }
   sq = infer_wave_sum(sq); sum = infer_wave_sum(sum);
-  unsigned e = __any(bad) ? INFER_ERR_LN_INPUT : 0;
+  unsigned cls = __any(bad) ? INFER_BAD_LAYERNORM : INFER_OK;
   const uint64_t n = (uint64_t)nn, m = (uint64_t)mult;
   const int64_t in = (int64_t)(n * m * sq - m * sum * sum) >> rcb;
-  if (!e && (in < -tmax || in >= tmax)) e = INFER_ERR_LN_TABLE;
-  if (e) {
-    if (lane == 0) { if (status) infer_refuse(status, row / per, INFER_BAD_LAYERNORM); else atomicOr(err, e); }
+  if (!cls && (in < -tmax || in >= tmax)) cls = INFER_BAD_LAYERNORM_TABLE;
+  if (cls) {
+    if (lane == 0) { infer_refuse(status, row / per, cls); if (cls == INFER_BAD_LAYERNORM) atomicCAS(status + row / per, INFER_BAD_LAYERNORM_TABLE, INFER_BAD_LAYERNORM); }
     for (size_t i = lane; i < fd; i += 64) o[row * fd + i] = 0;
     return;
   }
@@ -210,16 +208,16 @@ __global__ __launch_bounds__(256) void k_infer_layernorm(const int64_t* __restri
 }
 // Softmax::evaluate (softmax_op) after the shifts: element j of row i (rows of K words; i counts samples x C x R) is kept when j <= i mod R.
 // |masked| = low byte | high byte | exponential table index (tv bits) | zero chunks (zc groups of zv bits): table[index], times (chunk == 0) for
-// every group. |x| > 2^24 raises the error word (the index is masked: nothing is read outside the table, for any x and any shift). Checked mode
-// (per = words per sample): the host's shift step has already refused such a sample, or found it refused and given it zero shifts — the test
-// here then leaves its word as it is
+// every group. |x| > 2^24 refuses the sample (per = words per sample; the index is masked: nothing is read outside the table, for any x and any
+// shift): the host's shift step has already refused such a sample, or found it refused and given it zero shifts — the test here then leaves
+// its word as it is
 __global__ __launch_bounds__(256) void k_infer_softmax(const int64_t* __restrict__ x, const int64_t* __restrict__ shift, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n,
-                                                       size_t R, size_t K, int64_t scalar, int64_t neg_inf, unsigned tv, unsigned zc, unsigned zv, unsigned* err, unsigned* status, size_t per) {
+                                                       size_t R, size_t K, int64_t scalar, int64_t neg_inf, unsigned tv, unsigned zc, unsigned zv, unsigned* status, size_t per) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const size_t row = i / K, j = i % K;
   const int64_t v = x[i], lim = int64_t(1) << 24;
-  infer_flag(v < -lim || v > lim, i, per, status, INFER_BAD_SOFTMAX, err, INFER_ERR_SOFTMAX);
+  infer_flag(v < -lim || v > lim, i, per, status, INFER_BAD_SOFTMAX);
   const int64_t masked = j <= row % R ? (int64_t)((uint64_t)v * (uint64_t)scalar + (uint64_t)shift[row]) : neg_inf;
   int64_t r = masked < 0 ? (int64_t)(0 - (uint64_t)masked) : masked;
   r >>= 16;
@@ -249,174 +247,175 @@ struct InferDeviceState {
 };
 InferDeviceState* hip_infer_state_new(int device) { InferDeviceState* s = new InferDeviceState(); s->device = device; return s; }
 void hip_infer_state_free(InferDeviceState* s) { delete s; }
+// constants: on the device from the first launch that reads them on (freed with the model)
+static const int64_t* infer_const64(const InferProgram& p, InferDeviceState* st, int c) {
+  if (c < 0) return nullptr;
+  if (!st->c64[(size_t)c]) { int64_t* dp_ = nullptr; HIP_CHECK(hipMalloc((void**)&dp_, std::max<size_t>(p.consts[(size_t)c].n, 1) * 8)); st->c64[(size_t)c] = dp_; HIP_CHECK(hipMemcpy(dp_, p.consts[(size_t)c].data(), p.consts[(size_t)c].n * 8, hipMemcpyHostToDevice)); }
+  return st->c64[(size_t)c];
+}
+static const int8_t* infer_const8(const InferProgram& p, InferDeviceState* st, int c) {
+  if (!st->c8[(size_t)c]) { int8_t* dp_ = nullptr; HIP_CHECK(hipMalloc((void**)&dp_, p.consts[(size_t)c].w8.size())); st->c8[(size_t)c] = dp_; HIP_CHECK(hipMemcpy(dp_, p.consts[(size_t)c].w8.data(), p.consts[(size_t)c].w8.size(), hipMemcpyHostToDevice)); }
+  return st->c8[(size_t)c];
+}
+
+// The scratch of one chunk (outside the arenas, released before the call returns): [tensors, int64 | int8][input block][output block][one status
+// word per sample]; and the pinned block of the host side: the input block on its way up, the output block with the status words behind it on
+// its way down and, at the shift step of a Softmax, [its input of the chunk][the status words][the shifts]
+struct InferScratch {
+  bool in_q = true;     // model inputs within -128..127 (checked on the host, for the whole call): they travel as int8 and count as quantised tensors
+  std::vector<char> q;  // tensor t has an int8 copy
+  std::vector<size_t> off64, off8;
+  size_t chunk = 1, off_in = 0, off_out = 0, off_stat = 0, total = 0, sm_in = 0, sm_stat = 0, pinned_bytes = 0;
+  char* dev = nullptr; char* pinned = nullptr;
+  int64_t* T64(int t) const { return (int64_t*)(dev + off64[(size_t)t]); }
+  int8_t* T8(int t) const { return q[(size_t)t] ? (int8_t*)(dev + off8[(size_t)t]) : (int8_t*)nullptr; }
+  unsigned* status() const { return (unsigned*)(dev + off_stat); }
+  uint32_t* sm_status() const { return (uint32_t*)(pinned + sm_in); }
+};
+static InferScratch infer_layout(const InferProgram& p, const int64_t* inputs, size_t ninputs) {
+  const char* mbs = getenv("DP_INFER_SCRATCH_MB");
+  const size_t scratch_cap = (mbs && atoll(mbs) > 0 ? (size_t)atoll(mbs) : size_t(1024)) << 20, nt = p.tensors.size();
+  InferScratch m;
+  for (size_t i = 0, n = ninputs * p.input_len; i < n && m.in_q; i++) m.in_q = inputs[i] >= -128 && inputs[i] <= 127;
+  m.q.resize(nt); m.off64.resize(nt); m.off8.resize(nt);
+  size_t per_sample = 0;
+  auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+  for (size_t t = 0; t < nt; t++) { m.q[t] = p.tensors[t].q == IQ_YES || (p.tensors[t].q == IQ_IF_INPUTS && m.in_q); per_sample += p.tensors[t].len * (m.q[t] ? 9 : 8); }
+  per_sample += p.input_len * (m.in_q ? 1 : 8) + p.output_len * 8;
+  const size_t chunk = m.chunk = std::max<size_t>(1, std::min(ninputs, scratch_cap / std::max<size_t>(per_sample, 1)));
+  for (size_t t = 0; t < nt; t++) { m.off64[t] = m.total; m.total += up(chunk * p.tensors[t].len * 8); m.off8[t] = m.total; if (m.q[t]) m.total += up(chunk * p.tensors[t].len); }
+  const size_t in_bytes = chunk * p.input_len * (m.in_q ? 1 : 8), out_bytes = chunk * p.output_len * 8 + chunk * 4;
+  m.off_in = m.total; m.total += up(in_bytes);
+  m.off_out = m.total; m.off_stat = m.off_out + chunk * p.output_len * 8; m.total += up(out_bytes);
+  size_t sm_sh = 0;
+  for (const InferOp& o : p.ops) if (o.kind == IO_SOFTMAX) { m.sm_in = std::max(m.sm_in, up(chunk * p.tensors[(size_t)o.in0].len * 8)); sm_sh = std::max(sm_sh, chunk * p.tensors[(size_t)o.in1].len * 8); }
+  m.sm_stat = up(chunk * 4);
+  m.pinned_bytes = std::max(std::max(in_bytes, out_bytes), m.sm_in + m.sm_stat + sm_sh);
+  return m;
+}
+// The one table of what the host says of refused data: the message of a class (infer.h), and the order in which a plain call that met several
+// classes in a chunk names one
+static const char* const INFER_REFUSAL[] = {nullptr, "requant: value exceeds intermediate bit size", "embeddings: token outside the vocabulary", "gelu: input out of range", "layernorm: input out of range",
+                                            "softmax: input out of range", "layernorm: the inverse square root input leaves its table"};
+static uint32_t infer_first_class(const uint32_t* hs, size_t nb) {
+  for (uint32_t cls : {INFER_BAD_REQUANT, INFER_BAD_TOKEN, INFER_BAD_GELU, INFER_BAD_LAYERNORM, INFER_BAD_LAYERNORM_TABLE, INFER_BAD_SOFTMAX}) if (std::find(hs, hs + nb, cls) != hs + nb) return cls;
+  return INFER_OK;
+}
+static dim3 infer_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+// one op for the nb samples of the chunk: one launch. launches: by kind, [IO_KINDS + 2]: those of k_infer_gemm_i8
+static void infer_launch(const InferProgram& p, const InferOp& o, const InferScratch& m, InferDeviceState* st, hipStream_t s, size_t nb, size_t* launches) {
+  static const bool no_mfma = getenv("DP_INFER_NO_MFMA") && atoi(getenv("DP_INFER_NO_MFMA"));
+  auto c64 = [&](int c) { return infer_const64(p, st, c); };
+  const size_t len = p.tensors[(size_t)o.out].len, n = nb * len;
+  launches[o.kind]++;
+  switch (o.kind) {
+    case IO_GEMM:
+      if (!no_mfma && m.q[(size_t)o.in0] && !p.consts[(size_t)o.w].w8.empty()) {
+        const size_t M = nb * o.g.R;
+        k_infer_gemm_i8<<<dim3((unsigned)((M + IG_TM - 1) / IG_TM), (unsigned)((o.g.N + IG_TN - 1) / IG_TN)), 256, 0, s>>>(m.T8(o.in0), infer_const8(p, st, o.w), c64(o.bias), m.T64(o.out), M, o.g.K, o.g.N);
+        launches[IO_KINDS + 2]++;
+      } else k_infer_gemm_i64<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), p.tensors[(size_t)o.in0].len, c64(o.w), 0, c64(o.bias), m.T64(o.out), len, nb, o.g);
+      break;
+    case IO_GEMM2: k_infer_gemm_i64<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), p.tensors[(size_t)o.in0].len, m.T64(o.in1), p.tensors[(size_t)o.in1].len, nullptr, m.T64(o.out), len, nb, o.g); break;
+    case IO_REQUANT: k_infer_requant<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.out), m.T8(o.out), n, o.left, o.shift, o.bits, m.status(), len); break;
+    case IO_RELU: k_infer_relu<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.out), m.T8(o.out), n); break;
+    case IO_ADDC: k_infer_addc<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), m.T64(o.out), n, len, o.left, o.right); break;
+    case IO_ADD2: k_infer_add2<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.in1), m.T64(o.out), n, o.left, o.right); break;
+    case IO_EMBED: k_infer_embed<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), m.T64(o.out), n, o.d[0], o.d[1], m.status(), len); break;
+    case IO_MAXPOOL: k_infer_maxpool<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.out), m.T8(o.out), n, o.d[1], o.d[2]); break;
+    case IO_CONV: k_infer_conv<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), c64(o.bias), m.T64(o.out), n, o.d[0], o.d[1], o.d[2], o.d[3], o.d[4], o.d[5], o.d[6]); break;
+    case IO_GELU: k_infer_gelu<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.table), m.T64(o.out), n, o.left, (int64_t)o.d[0], m.status(), len); break;
+    case IO_LAYERNORM: {
+      const size_t rows = n / o.d[0];
+      k_infer_layernorm<<<infer_grid(rows * 64), 256, 0, s>>>(m.T64(o.in0), c64(o.w), c64(o.bias), c64(o.table), m.T64(o.out), rows, o.d[0], (int64_t)o.d[1], o.left, o.shift, m.status(), len / o.d[0]);
+      break;
+    }
+    case IO_SOFTMAX: k_infer_softmax<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.in1), c64(o.table), m.T64(o.out), n, o.d[1], o.d[2], o.left, -(((o.right >> 16) + 1) << 16), o.bits, (unsigned)o.d[3], (unsigned)o.d[4], m.status(), len); break;  // (after infer_shift_trip)
+    default: throw DpError(DP_ERR_ARG, "dp_model_infer: unknown op");
+  }
+}
+// The round trip in front of an IO_SOFTMAX: the shift of every row is made on the host, by the function the host inference calls. The status
+// words come down with the Softmax input: the samples refused so far are skipped (their rows are not read), those the range check refuses here
+// are marked, and the words go back to the device with the shifts. They are at m.sm_status() afterwards
+static void infer_shift_trip(const InferProgram& p, const InferOp& o, const InferScratch& m, hipStream_t s, size_t nb) {
+  const size_t nx = nb * p.tensors[(size_t)o.in0].len, nsh = nb * p.tensors[(size_t)o.in1].len;
+  int64_t* shifts = (int64_t*)(m.pinned + m.sm_in + m.sm_stat);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(m.sm_status(), m.status(), nb * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(m.pinned, m.T64(o.in0), nx * 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  p.shifts(o, (const int64_t*)m.pinned, nb, shifts, m.sm_status());
+  HIP_CHECK(hipMemcpyAsync(m.status(), m.sm_status(), nb * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(m.T64(o.in1), shifts, nsh * 8, hipMemcpyHostToDevice, s));
+}
 
 void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* inputs, size_t ninputs, int64_t* outputs, size_t out_stride, double* wall_ms, uint32_t* reasons) {
   HipDev* hd = static_cast<HipDev*>(d);
   hd->bind_thread(); hd->sync();
   hipStream_t s = hd->stream();
-  static const bool no_mfma = getenv("DP_INFER_NO_MFMA") && atoi(getenv("DP_INFER_NO_MFMA"));
   static const bool log_line = getenv("DP_INFER_LOG") && atoi(getenv("DP_INFER_LOG"));
-  const char* mbs = getenv("DP_INFER_SCRATCH_MB");
-  const size_t scratch_cap = (mbs && atoll(mbs) > 0 ? (size_t)atoll(mbs) : size_t(1024)) << 20;
   const auto t0 = std::chrono::steady_clock::now();
-  // model inputs within -128..127 (checked here, on the host, for the whole call): they travel as int8 and count as quantised tensors
-  bool in_q = true;
-  for (size_t i = 0, n = ninputs * p.input_len; i < n && in_q; i++) in_q = inputs[i] >= -128 && inputs[i] <= 127;
-  const size_t nt = p.tensors.size();
-  std::vector<char> q(nt);
-  size_t per_sample = 0;
-  auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-  for (size_t t = 0; t < nt; t++) { q[t] = p.tensors[t].q == IQ_YES || (p.tensors[t].q == IQ_IF_INPUTS && in_q); per_sample += p.tensors[t].len * (q[t] ? 9 : 8); }
-  per_sample += p.input_len * (in_q ? 1 : 8) + p.output_len * 8;
-  size_t chunk = std::max<size_t>(1, std::min(ninputs, scratch_cap / std::max<size_t>(per_sample, 1)));
-  // constants: on the device from the first launch that reads them on (freed with the model)
+  InferScratch m = infer_layout(p, inputs, ninputs);
+  const size_t chunk = m.chunk, in_w = m.in_q ? 1 : 8;
   st->c64.resize(p.consts.size(), nullptr); st->c8.resize(p.consts.size(), nullptr);
-  auto const64 = [&](int c) -> const int64_t* {
-    if (c < 0) return nullptr;
-    if (!st->c64[(size_t)c]) { int64_t* dp_ = nullptr; HIP_CHECK(hipMalloc((void**)&dp_, std::max<size_t>(p.consts[(size_t)c].n, 1) * 8)); st->c64[(size_t)c] = dp_; HIP_CHECK(hipMemcpy(dp_, p.consts[(size_t)c].data(), p.consts[(size_t)c].n * 8, hipMemcpyHostToDevice)); }
-    return st->c64[(size_t)c];
-  };
-  auto const8 = [&](int c) -> const int8_t* {
-    if (!st->c8[(size_t)c]) { int8_t* dp_ = nullptr; HIP_CHECK(hipMalloc((void**)&dp_, p.consts[(size_t)c].w8.size())); st->c8[(size_t)c] = dp_; HIP_CHECK(hipMemcpy(dp_, p.consts[(size_t)c].w8.data(), p.consts[(size_t)c].w8.size(), hipMemcpyHostToDevice)); }
-    return st->c8[(size_t)c];
-  };
-  // scratch of one chunk (outside the arenas, released before the call returns): [tensors, int64 | int8][input block][output block][error word]
-  // [checked mode: one status word per sample]
-  const bool checked = reasons != nullptr;
-  const size_t stat_bytes = checked ? chunk * 4 : 0;
-  std::vector<size_t> off64(nt), off8(nt);
-  size_t total = 0;
-  for (size_t t = 0; t < nt; t++) { off64[t] = total; total += up(chunk * p.tensors[t].len * 8); off8[t] = total; if (q[t]) total += up(chunk * p.tensors[t].len); }
-  const size_t in_bytes = chunk * p.input_len * (in_q ? 1 : 8), out_words = chunk * p.output_len + 1;
-  const size_t off_in = total; total += up(in_bytes);
-  const size_t off_out = total; total += up(out_words * 8 + stat_bytes);
-  // the shift step of a Softmax on the host side: [its input of the chunk][the error word, the status words][the shifts]
-  const size_t sm_mid = up(8 + stat_bytes);
-  size_t sm_in = 0, sm_sh = 0;
-  for (const InferOp& o : p.ops) if (o.kind == IO_SOFTMAX) { sm_in = std::max(sm_in, up(chunk * p.tensors[(size_t)o.in0].len * 8)); sm_sh = std::max(sm_sh, chunk * p.tensors[(size_t)o.in1].len * 8); }
-  char* scratch = nullptr; char* pinned = nullptr;
-  size_t launches[IO_KINDS + 2] = {0}, n_i8 = 0, n_i64 = 0, nchunks = 0, trips = 0, nrefused = 0;
+  size_t launches[IO_KINDS + 3] = {0}, nchunks = 0, trips = 0, nrefused = 0;
   double trip_ms = 0;
-  unsigned err = 0;
-  auto cleanup = [&] { (void)hipStreamSynchronize(s); if (scratch) (void)hipFree(scratch); if (pinned) (void)hipHostFree(pinned); scratch = pinned = nullptr; };
+  uint32_t stop = INFER_OK;  // plain mode (no `reasons`): the class of the refused sample that ends the call
+  auto cleanup = [&] { (void)hipStreamSynchronize(s); if (m.dev) (void)hipFree(m.dev); if (m.pinned) (void)hipHostFree(m.pinned); m.dev = m.pinned = nullptr; };
   try {
-    HIP_CHECK(hipMalloc((void**)&scratch, total));
-    HIP_CHECK(hipHostMalloc((void**)&pinned, std::max(std::max(in_bytes, out_words * 8 + stat_bytes), sm_in + sm_mid + sm_sh), hipHostMallocDefault));
-    auto T64 = [&](int t) { return (int64_t*)(scratch + off64[(size_t)t]); };
-    auto T8 = [&](int t) { return q[(size_t)t] ? (int8_t*)(scratch + off8[(size_t)t]) : (int8_t*)nullptr; };
-    int64_t* dout = (int64_t*)(scratch + off_out);
-    unsigned* derr = (unsigned*)(dout + chunk * p.output_len);
-    unsigned* dstat = checked ? (unsigned*)(dout + out_words) : nullptr;  // (null: the kernels raise the error word)
-    auto grid = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
-    for (size_t b0 = 0; b0 < ninputs && !err; b0 += chunk, nchunks++) {
-      const size_t nb = std::min(chunk, ninputs - b0), nin = nb * p.input_len;
-      if (in_q) { int8_t* h = (int8_t*)pinned; const int64_t* src = inputs + b0 * p.input_len; for (size_t i = 0; i < nin; i++) h[i] = (int8_t)src[i]; }
-      else memcpy(pinned, inputs + b0 * p.input_len, nin * 8);
-      HIP_CHECK(hipMemcpyAsync(scratch + off_in, pinned, nin * (in_q ? 1 : 8), hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemsetAsync(derr, 0, 8 + stat_bytes, s));
+    HIP_CHECK(hipMalloc((void**)&m.dev, m.total));
+    HIP_CHECK(hipHostMalloc((void**)&m.pinned, m.pinned_bytes, hipHostMallocDefault));
+    int64_t* dout = (int64_t*)(m.dev + m.off_out);
+    for (size_t b0 = 0; b0 < ninputs && !stop; b0 += chunk) {
+      const size_t nb = std::min(chunk, ninputs - b0), nin = nb * p.input_len, nout = nb * p.output_len;
+      nchunks++;
+      if (m.in_q) { int8_t* h = (int8_t*)m.pinned; const int64_t* src = inputs + b0 * p.input_len; for (size_t i = 0; i < nin; i++) h[i] = (int8_t)src[i]; }
+      else memcpy(m.pinned, inputs + b0 * p.input_len, nin * 8);
+      HIP_CHECK(hipMemcpyAsync(m.dev + m.off_in, m.pinned, nin * in_w, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemsetAsync(m.status(), 0, nb * 4, s));
       size_t ioff = 0;
       for (int t : p.inputs) {
         const size_t len = p.tensors[(size_t)t].len, n = nb * len;
-        k_infer_load<<<grid(n), 256, 0, s>>>(in_q ? nullptr : (const int64_t*)(scratch + off_in), in_q ? (const int8_t*)(scratch + off_in) : nullptr, p.input_len, ioff, len, T64(t), T8(t), n);
+        k_infer_load<<<infer_grid(n), 256, 0, s>>>(m.in_q ? nullptr : (const int64_t*)(m.dev + m.off_in), m.in_q ? (const int8_t*)(m.dev + m.off_in) : nullptr, p.input_len, ioff, len, m.T64(t), m.T8(t), n);
         ioff += len; launches[IO_KINDS]++;
       }
       for (const InferOp& o : p.ops) {
-        if (err) break;
-        const size_t n = nb * p.tensors[(size_t)o.out].len;
-        launches[o.kind]++;
-        switch (o.kind) {
-          case IO_GEMM: {
-            const bool i8 = !no_mfma && q[(size_t)o.in0] && !p.consts[(size_t)o.w].w8.empty();
-            if (i8) {
-              const size_t M = nb * o.g.R;
-              k_infer_gemm_i8<<<dim3((unsigned)((M + IG_TM - 1) / IG_TM), (unsigned)((o.g.N + IG_TN - 1) / IG_TN)), 256, 0, s>>>(T8(o.in0), const8(o.w), const64(o.bias), T64(o.out), M, o.g.K, o.g.N);
-              n_i8++;
-            } else {
-              k_infer_gemm_i64<<<grid(n), 256, 0, s>>>(T64(o.in0), p.tensors[(size_t)o.in0].len, const64(o.w), 0, const64(o.bias), T64(o.out), p.tensors[(size_t)o.out].len, nb, o.g);
-              n_i64++;
-            }
-            break;
-          }
-          case IO_GEMM2:
-            k_infer_gemm_i64<<<grid(n), 256, 0, s>>>(T64(o.in0), p.tensors[(size_t)o.in0].len, T64(o.in1), p.tensors[(size_t)o.in1].len, nullptr, T64(o.out), p.tensors[(size_t)o.out].len, nb, o.g);
-            n_i64++;
-            break;
-          case IO_REQUANT: k_infer_requant<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.out), T8(o.out), n, o.left, o.shift, o.bits, derr, dstat, p.tensors[(size_t)o.out].len); break;
-          case IO_RELU: k_infer_relu<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.out), T8(o.out), n); break;
-          case IO_ADDC: k_infer_addc<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.w), T64(o.out), n, p.tensors[(size_t)o.out].len, o.left, o.right); break;
-          case IO_ADD2: k_infer_add2<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.in1), T64(o.out), n, o.left, o.right); break;
-          case IO_EMBED: k_infer_embed<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.w), T64(o.out), n, o.d[0], o.d[1], derr, dstat, p.tensors[(size_t)o.out].len); break;
-          case IO_MAXPOOL: k_infer_maxpool<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.out), T8(o.out), n, o.d[1], o.d[2]); break;
-          case IO_CONV: k_infer_conv<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.w), const64(o.bias), T64(o.out), n, o.d[0], o.d[1], o.d[2], o.d[3], o.d[4], o.d[5], o.d[6]); break;
-          case IO_GELU: k_infer_gelu<<<grid(n), 256, 0, s>>>(T64(o.in0), const64(o.table), T64(o.out), n, o.left, (int64_t)o.d[0], derr, dstat, p.tensors[(size_t)o.out].len); break;
-          case IO_LAYERNORM: {
-            const size_t rows = n / o.d[0];
-            k_infer_layernorm<<<grid(rows * 64), 256, 0, s>>>(T64(o.in0), const64(o.w), const64(o.bias), const64(o.table), T64(o.out), rows, o.d[0], (int64_t)o.d[1], o.left, o.shift, derr, dstat, p.tensors[(size_t)o.out].len / o.d[0]);
-            break;
-          }
-          case IO_SOFTMAX: {
-            // the shift of every row is made on the host, by the function the host inference calls. The error word comes first: rows that follow
-            // bad data are not read. Checked mode: the status words take its place — the samples refused so far are skipped, those the range check
-            // refuses here are marked, and the words go back to the device with the shifts
-            const auto ts = std::chrono::steady_clock::now();
-            const size_t nx = nb * p.tensors[(size_t)o.in0].len, nsh = nb * p.tensors[(size_t)o.in1].len;
-            const int64_t* table = const64(o.table);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(pinned + sm_in, derr, 8 + nb * (checked ? 4 : 0), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipMemcpyAsync(pinned, T64(o.in0), nx * 8, hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            err = *(const unsigned*)(pinned + sm_in);
-            if (checked) {
-              p.shifts_checked(o, (const int64_t*)pinned, nb, (int64_t*)(pinned + sm_in + sm_mid), (uint32_t*)(pinned + sm_in + 8));
-              HIP_CHECK(hipMemcpyAsync(dstat, pinned + sm_in + 8, nb * 4, hipMemcpyHostToDevice, s));
-            } else if (!err && !p.shifts(o, (const int64_t*)pinned, nb, (int64_t*)(pinned + sm_in + sm_mid))) err = INFER_ERR_SOFTMAX;
-            if (!err) {
-              HIP_CHECK(hipMemcpyAsync(T64(o.in1), pinned + sm_in + sm_mid, nsh * 8, hipMemcpyHostToDevice, s));
-              k_infer_softmax<<<grid(n), 256, 0, s>>>(T64(o.in0), T64(o.in1), table, T64(o.out), n, o.d[1], o.d[2], o.left, -(((o.right >> 16) + 1) << 16), o.bits, (unsigned)o.d[3], (unsigned)o.d[4], derr,
-                                                      dstat, p.tensors[(size_t)o.out].len);
-            }
-            trips++; trip_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
-            break;
-          }
-          default: throw DpError(DP_ERR_ARG, "dp_model_infer: unknown op");
+        if (o.kind == IO_SOFTMAX) {
+          const auto ts = std::chrono::steady_clock::now();
+          infer_shift_trip(p, o, m, s, nb);
+          trips++; trip_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
+          if (!reasons && (stop = infer_first_class(m.sm_status(), nb))) break;
         }
+        infer_launch(p, o, m, st, s, nb, launches);
       }
-      if (err) { nchunks++; break; }
+      if (stop) break;
       size_t ooff = 0;
       for (int t : p.outputs) {
         const size_t len = p.tensors[(size_t)t].len, n = nb * len;
-        k_infer_store<<<grid(n), 256, 0, s>>>(T64(t), len, dout, p.output_len, ooff, n);
+        k_infer_store<<<infer_grid(n), 256, 0, s>>>(m.T64(t), len, dout, p.output_len, ooff, n);
         ooff += len; launches[IO_KINDS + 1]++;
       }
       HIP_CHECK(hipGetLastError());
-      // the outputs, the error word behind them and (checked mode) the status words behind that: one copy (a partial last chunk: the words
-      // are fetched on their own)
-      const size_t nout = nb * p.output_len, tail = 8 + nb * (checked ? 4 : 0);
-      if (nb == chunk) HIP_CHECK(hipMemcpyAsync(pinned, dout, nout * 8 + tail, hipMemcpyDeviceToHost, s));
-      else { HIP_CHECK(hipMemcpyAsync(pinned, dout, nout * 8, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipMemcpyAsync(pinned + nout * 8, derr, tail, hipMemcpyDeviceToHost, s)); }
+      // the outputs and the status words behind them: one copy (a partial last chunk: the words are fetched on their own)
+      if (nb == chunk) HIP_CHECK(hipMemcpyAsync(m.pinned, dout, nout * 8 + nb * 4, hipMemcpyDeviceToHost, s));
+      else { HIP_CHECK(hipMemcpyAsync(m.pinned, dout, nout * 8, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipMemcpyAsync(m.pinned + nout * 8, m.status(), nb * 4, hipMemcpyDeviceToHost, s)); }
       HIP_CHECK(hipStreamSynchronize(s));
-      err = *(const unsigned*)(pinned + nout * 8);  // (checked mode: nothing raises it)
-      if (checked) {  // refused samples: the reason, and zeros for whatever the later kernels made of them
-        const uint32_t* hs = (const uint32_t*)(pinned + nout * 8 + 8);
-        for (size_t i = 0; i < nb; i++) {
-          reasons[b0 + i] = hs[i];
-          if (hs[i]) { memset(outputs + (b0 + i) * out_stride, 0, p.output_len * 8); nrefused++; }
-          else memcpy(outputs + (b0 + i) * out_stride, pinned + i * p.output_len * 8, p.output_len * 8);
-        }
-      } else
-      if (!err) for (size_t i = 0; i < nb; i++) memcpy(outputs + (b0 + i) * out_stride, pinned + i * p.output_len * 8, p.output_len * 8);
+      const uint32_t* hs = (const uint32_t*)(m.pinned + nout * 8);
+      if (!reasons && (stop = infer_first_class(hs, nb))) break;  // (none of the chunk's rows is copied out)
+      for (size_t i = 0; i < nb; i++) {  // refused samples (checked mode): the public reason, and zeros for whatever the later kernels made of them
+        const uint32_t cls = hs[i] == INFER_BAD_LAYERNORM_TABLE ? INFER_BAD_LAYERNORM : hs[i];
+        if (reasons) reasons[b0 + i] = cls;
+        if (cls) { memset(outputs + (b0 + i) * out_stride, 0, p.output_len * 8); nrefused++; }
+        else memcpy(outputs + (b0 + i) * out_stride, m.pinned + i * p.output_len * 8, p.output_len * 8);
+      }
     }
   } catch (...) { cleanup(); throw; }
   cleanup();
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (wall_ms) *wall_ms = ms;
+  const size_t n_i8 = launches[IO_KINDS + 2], n_i64 = launches[IO_GEMM] + launches[IO_GEMM2] - n_i8;
   if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu conv %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s\n",
                    n_i8, n_i64, launches[IO_CONV], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], trips, trip_ms,
-                   ninputs, nchunks, chunk, (double)total / 1048576.0, in_q ? "int8" : "int64", ms, checked ? ("; checked, refused " + std::to_string(nrefused)).c_str() : "");
-  DP_REQUIRE(!(err & INFER_ERR_REQUANT), DP_ERR_ARG, "requant: value exceeds intermediate bit size");
-  DP_REQUIRE(!(err & INFER_ERR_TOKEN), DP_ERR_ARG, "embeddings: token outside the vocabulary");
-  DP_REQUIRE(!(err & INFER_ERR_GELU), DP_ERR_ARG, "gelu: input out of range");
-  DP_REQUIRE(!(err & INFER_ERR_LN_INPUT), DP_ERR_ARG, "layernorm: input out of range");
-  DP_REQUIRE(!(err & INFER_ERR_LN_TABLE), DP_ERR_ARG, "layernorm: the inverse square root input leaves its table");
-  DP_REQUIRE(!(err & INFER_ERR_SOFTMAX), DP_ERR_ARG, "softmax: input out of range");
+                   ninputs, nchunks, chunk, (double)m.total / 1048576.0, m.in_q ? "int8" : "int64", ms, reasons ? ("; checked, refused " + std::to_string(nrefused)).c_str() : "");
+  DP_REQUIRE(!stop, DP_ERR_ARG, INFER_REFUSAL[stop]);
 }

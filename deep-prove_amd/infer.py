@@ -35,23 +35,28 @@ def _load():
     return _bound
 
 
-def infer(ctx, inputs_i64, all_kinds=False, flags=None):
-    """Model::run for every row of inputs_i64[n, ninput] on the context's GPU; returns (outputs[n, nout], wall_ms). The integers are those of
-    infer_host, row by row. Models with LayerNorm / Softmax / Mha / GELU nodes raise DeepProveError (DP_ERR_ARG) unless all_kinds is set
-    (dp_model_infer_ex with DP_INFER_ALL_KINDS: the Softmax row shifts are computed on the host). flags: the raw flag word, instead of all_kinds."""
+def _prepare(ctx, inputs_i64, all_kinds, flags):
+    """(lib, inputs [n][ninput] contiguous int64, outputs [n][output length] to be written, flag word)"""
     lib = _load()
     x = np.ascontiguousarray(inputs_i64, dtype=np.int64)
     if x.ndim == 1:
         x = x.reshape(1, -1)
-    n, ninput = x.shape
+    n, _ = x.shape  # (two dimensions)
     cap = C.c_size_t(0)
     check(lib.dp_model_output_len(ctx.h, C.byref(cap)))
-    outs = np.empty((n, cap.value), dtype=np.int64)
-    no = C.c_size_t(0)
-    ms = C.c_double()
     if flags is None:
         flags = ALL_KINDS if all_kinds else 0
-    check(lib.dp_model_infer_ex(ctx.h, x.ctypes.data_as(i64p), n, ninput, flags, outs.ctypes.data_as(i64p), cap.value, C.byref(no), C.byref(ms)))
+    return lib, x, np.empty((n, cap.value), dtype=np.int64), flags
+
+
+def infer(ctx, inputs_i64, all_kinds=False, flags=None):
+    """Model::run for every row of inputs_i64[n, ninput] on the context's GPU; returns (outputs[n, nout], wall_ms). The integers are those of
+    infer_host, row by row. Models with LayerNorm / Softmax / Mha / GELU nodes raise DeepProveError (DP_ERR_ARG) unless all_kinds is set
+    (dp_model_infer_ex with DP_INFER_ALL_KINDS: the Softmax row shifts are computed on the host). flags: the raw flag word, instead of all_kinds."""
+    lib, x, outs, flags = _prepare(ctx, inputs_i64, all_kinds, flags)
+    no = C.c_size_t(0)
+    ms = C.c_double()
+    check(lib.dp_model_infer_ex(ctx.h, x.ctypes.data_as(i64p), x.shape[0], x.shape[1], flags, outs.ctypes.data_as(i64p), outs.shape[1], C.byref(no), C.byref(ms)))
     return outs[:, :no.value].copy(), ms.value
 
 
@@ -59,20 +64,11 @@ def infer_checked(ctx, inputs_i64, all_kinds=False, flags=None):
     """dp_model_infer_checked: infer() with a status per input; returns (outputs[n, nout], reasons[n] uint32, wall_ms). reasons[i] == 0: row i is
     that of infer_host. Otherwise infer_host refuses input i with DP_ERR_ARG, reasons[i] is the class of the first node that does (REASONS) and
     row i is zeros. Errors of the model or the call (a refused kind, unknown flag bits, shapes) raise DeepProveError as infer() does."""
-    lib = _load()
-    x = np.ascontiguousarray(inputs_i64, dtype=np.int64)
-    if x.ndim == 1:
-        x = x.reshape(1, -1)
-    n, ninput = x.shape
-    cap = C.c_size_t(0)
-    check(lib.dp_model_output_len(ctx.h, C.byref(cap)))
-    outs = np.empty((n, cap.value), dtype=np.int64)
-    reasons = np.zeros(n, dtype=np.uint32)
+    lib, x, outs, flags = _prepare(ctx, inputs_i64, all_kinds, flags)
+    reasons = np.zeros(x.shape[0], dtype=np.uint32)
     no, nref = C.c_size_t(0), C.c_size_t(0)
     ms = C.c_double()
-    if flags is None:
-        flags = ALL_KINDS if all_kinds else 0
-    check(lib.dp_model_infer_checked(ctx.h, x.ctypes.data_as(i64p), n, ninput, flags, outs.ctypes.data_as(i64p), cap.value, C.byref(no),
+    check(lib.dp_model_infer_checked(ctx.h, x.ctypes.data_as(i64p), x.shape[0], x.shape[1], flags, outs.ctypes.data_as(i64p), outs.shape[1], C.byref(no),
                                      reasons.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(nref), C.byref(ms)))
     assert nref.value == int(np.count_nonzero(reasons))
     return outs[:, :no.value].copy(), reasons, ms.value

@@ -19,10 +19,12 @@
  * Errors in the data are the host's: a Requant input beyond 2^intermediate_bit_size, an Embeddings token outside the vocabulary and, under
  * DP_INFER_ALL_KINDS, a GELU input beyond 2^20 or outside its table ("gelu: ..."), a LayerNorm input beyond 2^20 or a row whose variance leaves
  * the inverse-square-root table ("layernorm: ..."), a Softmax input beyond 2^24 ("softmax: ...") make the whole call return DP_ERR_ARG (as
- * dp_model_infer_host does for that input); the model stays usable. The device error word is read before the host computes any shift, so no
- * row that follows bad data reaches expf. Flag bits other than DP_INFER_ALL_KINDS: DP_ERR_ARG.
+ * dp_model_infer_host does for that input); the model stays usable. The call ends at the first chunk of the batch that holds such an input, with
+ * the message the host has for it, and writes none of that chunk's rows. The device marks refused inputs one by one (below) and the host
+ * reads the marks before it computes any shift, so no row that follows bad data reaches expf. Flag bits other than DP_INFER_ALL_KINDS: DP_ERR_ARG.
  *
- * dp_model_infer_checked refuses such data input by input instead: the call returns DP_OK, every chunk of the batch is processed, and
+ * dp_model_infer_checked hands the same marks to the caller and refuses such data input by input instead: the call returns DP_OK, every chunk of
+ * the batch is processed, and
  * reasons[i] says whether input i was inferred (DP_INFER_OK: its row holds the integers of dp_model_infer_host) or which kind of node refused
  * it first, in node order (DP_INFER_BAD_*: dp_model_infer_host returns DP_ERR_ARG for that input with the message of that class; its row is
  * zeros). On the device every sample of a chunk has a status word that only the first refusal writes; a refused sample's values travel on

@@ -24,8 +24,9 @@ def _numpy(mb, xs):
     return np.stack([mb.run(x) for x in xs])
 
 
-def _child(tmp_path, calls):
-    """calls: [(model, inputs[batch][input_len], mode)] -> per call a dict: out, error, reasons, counts (launches by name), inputs ("int8" | "int64")"""
+def _child(tmp_path, calls, **env):
+    """calls: [(model, inputs[batch][input_len], mode)] -> per call a dict: out, error, reasons, counts (launches by name), inputs ("int8" | "int64").
+    env: further environment variables of the child"""
     models = []
     for mb, _, _ in calls:
         if not any(mb is m for m in models):
@@ -39,7 +40,7 @@ def _child(tmp_path, calls):
         data["model_%d" % pos], data["x_%d" % pos], data["mode_%d" % pos] = index(calls[c][0]), np.ascontiguousarray(calls[c][1], dtype=np.int64), calls[c][2]
     src, res = str(tmp_path / "cases.npz"), str(tmp_path / "out.npz")
     np.savez(src, **data)
-    r = subprocess.run([sys.executable, CHILD, src, res], capture_output=True, text=True, timeout=600, env=dict(os.environ, DP_INFER_LOG="1"))
+    r = subprocess.run([sys.executable, CHILD, src, res], capture_output=True, text=True, timeout=600, env=dict(os.environ, DP_INFER_LOG="1", **env))
     assert r.returncode == 0 and "infer edges child ok" in r.stdout, r.stdout[-500:] + r.stderr[-2000:]
     lines = [ln for ln in r.stderr.split("\n") if ln.startswith("[dp infer]")]
     assert len(lines) == len(calls), r.stderr[-2000:]
@@ -295,3 +296,54 @@ def test_a_bad_run_across_a_wave_boundary_inside_a_sample(dev):
         _checked_equals_host(ctx, blob, xs, True, [3, 5, 6])
     finally:
         ctx.free()
+
+
+# ---- (l) what a plain call makes of the status words
+
+@pytest.mark.parametrize("table_first", [True, False])
+def test_both_layernorm_messages_in_one_chunk(dev, table_first):
+    """layernorm_mlp(4, 2, 16), batch 4: inputs 1 and 2 are the layernorm_2 edge's first row that "leaves its table" and its single 2^20 + 1 row, in
+    both orders, between two good inputs. The plain call names "input out of range" either way (the host's two LayerNorm messages keep their
+    order, whichever sample comes first); the checked call knows one class for both"""
+    import deep_prove_amd as dpa
+    e = E.layernorm_edge(2)
+    table = [x for x, _, fragment in e.bad if fragment == "leaves its table"][0]
+    rng = [x for x, _, fragment in e.bad if fragment == "input out of range"][0]
+    assert np.abs(rng).max() == (1 << 20) + 1
+    xs = np.stack([e.good[0], table, rng, e.good[1]] if table_first else [e.good[0], rng, table, e.good[1]])
+    blob = e.mb.blob()
+    want = _numpy(e.mb, xs[[0, 3]])
+    hrows, hreasons, msgs = E.host(blob, xs, want.shape[1])
+    assert list(hreasons) == [0, 4, 4, 0] and sorted(("leaves its table" in m, "input out of range" in m) for m in msgs[1:3]) == [(False, True), (True, False)], msgs
+    ctx = dpa.Context.generate(dev, blob)
+    try:
+        with pytest.raises(dpa.DeepProveError) as ei:
+            ctx.infer(xs, all_kinds=True)
+        assert ei.value.code == -1 and "layernorm: input out of range" in str(ei.value) and "table" not in str(ei.value), str(ei.value)
+        out, reasons, _ = ctx.infer_checked(xs, all_kinds=True)
+        assert list(reasons) == [0, 4, 4, 0] and (reasons == hreasons).all(), reasons
+        assert not out[[1, 2]].any() and (out[[0, 3]] == want).all() and (out == hrows).all()
+    finally:
+        ctx.free()
+
+
+def test_plain_call_refused_in_a_later_chunk(tmp_path):
+    """gelu_only(128), batch 700 under a scratch bound of 1 MB (three chunks at least): one refused value in the last input. The plain call raises
+    the GELU's message — after the chunks before it went through —, the same batch without the value gives numpy's rows, the checked call refuses
+    exactly that input"""
+    import deep_prove_amd as dpa
+    mb = dpa.models.gelu_only(128, config=31)
+    good = np.stack([mb.input(1000 + i) for i in range(700)])
+    bad = good.copy()
+    bad[699, 77] = E.gelu_edges(mb.layers[0])[1] + 1
+    plain, refused, checked = _child(tmp_path, [(mb, good, E.ALL_KINDS), (mb, bad, E.ALL_KINDS), (mb, bad, E.ALL_KINDS | E.CHECKED)], DP_INFER_SCRATCH_MB="1")
+    for g in (plain, refused, checked):
+        m = re.search(r"batch 700 in (\d+) chunks of (\d+),", g["line"])
+        assert m and int(m.group(1)) >= 3 and int(m.group(1)) == -(-700 // int(m.group(2))), g["line"]  # (the bad input sits in the last chunk, and the plain call got there)
+    want = _numpy(mb, good)
+    assert plain["error"] == "" and (plain["out"] == want).all()
+    assert "gelu: input out of range" in refused["error"] and refused["out"].size == 0, refused["error"]
+    hrows, hreasons, _ = E.host(mb.blob(), bad[696:], want.shape[1])
+    assert list(hreasons) == [0, 0, 0, 3]
+    assert checked["error"] == "" and list(checked["reasons"]) == [0] * 699 + [3] and not checked["out"][699].any() and (checked["out"][:699] == want[:699]).all()
+    assert (checked["out"][696:] == hrows).all()
