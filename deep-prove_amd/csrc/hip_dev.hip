@@ -360,7 +360,7 @@ class HipDev : public Dev {
     wait_exit_(t0);
   }
   u64* dres_ = nullptr;   // device result buffer
-  unsigned* fused_ticket_ = nullptr;  // "last workgroup" ticket of k_sc_fused (device, zero between launches)
+  unsigned* fused_ticket_ = nullptr;  // "last workgroup" ticket of k_sc_fused, k_classic_fused_pub, k_bf_fold_msg / k_bf_msg (device, zero between launches: round_ticket_now)
   void* hstage_ = nullptr;  // pinned + device-mapped staging of bulk copies (from DESC_BYTES on; coherent: k_download's chunk tags are polled by the host)
   char* hstage_dev_ = nullptr;
   void* hdesc_ = nullptr;   // descriptor ring: written by the host before a launch, read by its kernels (host_ro_flags: non-coherent, cacheable on the GPU)
@@ -1658,8 +1658,9 @@ class HipDev : public Dev {
         Ext* partial = (Ext*)arena_alloc((size_t)g * 4 * 16);
         nb_ = bytes;
         const bool skip1 = claim_hint_ != nullptr;
-        // one proof on the GPU: the kernel's last workgroup reduces and publishes (no second launch); cohort members keep the
-        // separate reduction (their workgroups of one launch belong to different proofs)
+        // one proof on the GPU: the kernel's last workgroup reduces and publishes (no second launch). Cohort members still keep the separate
+        // reduction HERE — not because a merged launch mixes proofs (each blockIdx.z has its own pack, hence its own ticket, result and flag: classic_round
+        // and bf_round publish this way inside cohorts), but because no test drives a sumcheck of this size through a cohort yet.
         // (round 2 had this OFF: its agent-scope release fence per workgroup wrote the XCD's whole L2 back 4096 times per launch, 162 / 40 us -> 1122 / 230 us.
         // Round 4 publishes the 64 bytes of block sums write-through instead — kernels.inc, k_sc_fused — and it is the default; DP_FUSED_TICKET=0 restores the
         // separate 14 us reduction launch per round.)
@@ -2050,6 +2051,15 @@ class HipDev : public Dev {
     }
     nb_ = bytes; DPL(k_eq_outer_many, dim3(grid_for(maxn, 64), (unsigned)n), dim3(TPB), dd);
   }
+  // The rounds of the batch opening (classic_round, bf_round) publish from the last workgroup of their streaming kernel, with fused_ticket_ as the ticket.
+  // ONE ticket word per context is enough: every kernel that takes tickets is followed by the host's wait for what it publishes before the context launches
+  // anything else, a context launches on one stream (its own, or its cohort's, where its packs of two launches never share a launch), and the last workgroup
+  // writes the zero back before the kernel ends. Not with the sums on other ranks (share_x_) or without zero-copy results. DP_CLASSIC_TICKET=0 (read once):
+  // the separate reduction launches.
+  bool round_ticket_now() const {
+    static const bool env = knob("DP_CLASSIC_TICKET", 1) != 0;
+    return env && zerocopy_ && !share_x_ && fused_ticket_ != nullptr;
+  }
   void classic_round(DBuf* fs, DBuf* eqs, DBuf* los, int np, const Ext* r, Ext* out) override {
     DP_REQUIRE((size_t)np * (sizeof(PolyDesc) * 2 + sizeof(ClassicDesc) + 4) + 320 <= DESC_BYTES && (size_t)np * 4 <= RES_WORDS && np * 2 <= 1024, DP_ERR_SHAPE, "classic_round: too many polynomials");
     if (desc_off_ + (size_t)np * (sizeof(PolyDesc) * 2 + sizeof(ClassicDesc) + 4) + 320 > DESC_BYTES) stream_wait();
@@ -2093,9 +2103,14 @@ class HipDev : public Dev {
       first[np] = nblk;
       Ext* partial = (Ext*)arena_alloc((size_t)nblk * 2 * 16);
       unsigned long long seq = ++seq_;
-      nb_ = bytes; DPL(k_classic_fused, dim3(nblk), dim3(TPB), fd, cdd, np, r ? *r : ex_zero(), r ? 1 : 0, partial);
-      DP_REQUIRE(2 * np <= 1024, DP_ERR_SHAPE, "classic round: too many polynomials for one reduction");
-      nb_ = 0; DPL(k_classic_reduce, dim3(1), dim3(np >= 8 && !throughput_mode_ ? 1024 : 256), fd, np, (const Ext*)partial, (Ext*)hres_dev_, hflag_dev_, seq);
+      DP_REQUIRE(2 * np <= REDUCE_LDS_VALUES, DP_ERR_SHAPE, "classic round: too many polynomials for one reduction");
+      // the last workgroup of the fused launch reduces and publishes (k_classic_fused_pub), members of a cohort included: a member brings its own ticket,
+      // result and flag in its argument pack. DP_CLASSIC_TICKET=0: the separate one-workgroup reduction launch per round, as before.
+      if (round_ticket_now()) { nb_ = bytes; DPL(k_classic_fused_pub, dim3(nblk), dim3(TPB), fd, cdd, np, r ? *r : ex_zero(), r ? 1 : 0, partial, fused_ticket_, (Ext*)hres_dev_, hflag_dev_, seq); }
+      else {
+        nb_ = bytes; DPL(k_classic_fused, dim3(nblk), dim3(TPB), fd, cdd, np, r ? *r : ex_zero(), r ? 1 : 0, partial);
+        nb_ = 0; DPL(k_classic_reduce, dim3(1), dim3(np >= 8 && !throughput_mode_ ? 1024 : 256), fd, np, (const Ext*)partial, (Ext*)hres_dev_, hflag_dev_, seq);
+      }
       wait_flag(seq, (size_t)np * 4);
       for (int i = 0; i < 2 * np; i++) out[i] = ex(hres_[2 * i], hres_[2 * i + 1]);
       release(mk);
@@ -2141,14 +2156,31 @@ class HipDev : public Dev {
   }
   void bf_round(DBuf& eq, DBuf& f, const Ext* ch, Ext* msg) override {
     DP_REQUIRE(eq.ext && f.ext && eq.n == f.n, DP_ERR_SHAPE, "bf_round: shapes");
+    const bool pub = round_ticket_now();
+    if (ch && msg && pub && f.n > 2 && f.n % 4 == 0) {
+      // fold and message in one pass over eq and f, published by the kernel's last workgroup (k_bf_fold_msg): one launch before the wait instead of three
+      DBuf fo = alloc(f.n / 2, true), eo = alloc(eq.n / 2, true);
+      const size_t nquads = f.n / 4;
+      size_t mk = mark();
+      int g = grid_for(nquads, 512);
+      Ext* partial = (Ext*)arena_alloc((size_t)g * 3 * 16);
+      unsigned long long seq = ++seq_;
+      nb_ = 48.0 * f.n; DPL(k_bf_fold_msg, dim3(g), dim3(TPB), (const Ext*)f.p, (const Ext*)eq.p, (Ext*)fo.p, (Ext*)eo.p, nquads, *ch, partial, fused_ticket_, (Ext*)hres_dev_, hflag_dev_, seq);
+      wait_flag(seq, 6);
+      for (int i = 0; i < 3; i++) msg[i] = ex(hres_[2 * i], hres_[2 * i + 1]);
+      release(mk);
+      f = fo; eq = eo;
+      return;
+    }
     if (ch) { DBuf t[2] = {eq, f}; fold_tables(t, 2, *ch); eq = t[0]; f = t[1]; }
     if (!msg) return;
     if (f.n == 1) { u64 w[2]; download(f, w); msg[0] = msg[1] = msg[2] = ex(w[0], w[1]); return; }
     size_t mk = mark();
     int g = grid_for(f.n / 2, 512);
-    Ext* partial = (Ext*)arena_alloc((size_t)g * 4 * 16);
-    nb_ = 32.0 * f.n; DPL(k_bf_msg, dim3(g), dim3(TPB), (const Ext*)f.p, (const Ext*)eq.p, f.n / 2, partial);
-    reduce_publish(partial, (size_t)g, 4, 3);
+    Ext* partial = (Ext*)arena_alloc((size_t)g * 3 * 16);
+    unsigned long long seq = pub ? ++seq_ : 0;
+    nb_ = 32.0 * f.n; DPL(k_bf_msg, dim3(g), dim3(TPB), (const Ext*)f.p, (const Ext*)eq.p, f.n / 2, partial, pub ? fused_ticket_ : (unsigned*)nullptr, (Ext*)hres_dev_, hflag_dev_, seq);
+    if (pub) wait_flag(seq, 6); else reduce_publish(partial, (size_t)g, 3, 3);
     for (int i = 0; i < 3; i++) msg[i] = ex(hres_[2 * i], hres_[2 * i + 1]);
     release(mk);
   }

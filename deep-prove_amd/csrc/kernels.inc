@@ -843,20 +843,32 @@ KBODY k_axpy_rep(Ext* acc, const void* x, int xext, Ext coeff, size_t n_acc, uns
   }
 }
 // K10 message on evaluation-form pairs: [sum a*ea, sum ((b-a)*ea + a*(eb-ea)), sum (b-a)(eb-ea)]
-KBODY k_bf_msg(const Ext* f, const Ext* eq, size_t npairs, Ext* partial) {
+// partial[3 * block + {0,1,2}]; `counter` non-null: the last workgroup adds the blocks up and publishes the three sums itself (sc_block_sums_finish)
+__device__ __forceinline__ void bf_msg_acc(Ext a, Ext a1, Ext ea, Ext e1, Ext* c) {
+  Ext b = ex_sub(a1, a), eb = ex_sub(e1, ea);
+  c[0] = ex_add(c[0], ex_mul(a, ea));
+  c[1] = ex_add(c[1], ex_add(ex_mul(b, ea), ex_mul(a, eb)));
+  c[2] = ex_add(c[2], ex_mul(b, eb));
+}
+KBODY k_bf_msg(const Ext* f, const Ext* eq, size_t npairs, Ext* partial, unsigned* counter, Ext* result, unsigned long long* flag, unsigned long long seq) {
   __shared__ Ext sm[TPB / 64];
-  Ext c0 = ex_zero(), c1 = ex_zero(), c2 = ex_zero();
-  for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < npairs; j += (size_t)gridDim.x * blockDim.x) {
-    Ext a = f[2 * j], b = ex_sub(f[2 * j + 1], a), ea = eq[2 * j], eb = ex_sub(eq[2 * j + 1], ea);
-    c0 = ex_add(c0, ex_mul(a, ea));
-    c1 = ex_add(c1, ex_add(ex_mul(b, ea), ex_mul(a, eb)));
-    c2 = ex_add(c2, ex_mul(b, eb));
+  Ext c[3] = {ex_zero(), ex_zero(), ex_zero()};
+  for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < npairs; j += (size_t)gridDim.x * blockDim.x) bf_msg_acc(f[2 * j], f[2 * j + 1], eq[2 * j], eq[2 * j + 1], c);
+  sc_block_sums_finish<3>(c, sm, partial, counter, result, flag, seq);
+}
+// One commit-phase round after the first in ONE pass (Dev::bf_round with a challenge): each lane takes four consecutive entries of f and of eq, folds them with
+// ch into two (k_fold's formula: the stored tables are k_fold's word for word), stores those and adds the folded pair to k_bf_msg's sums — the folded
+// tables are not read back for the message, and the last workgroup publishes it (no k_reduce_publish launch).
+KBODY k_bf_fold_msg(const Ext* f, const Ext* eq, Ext* fout, Ext* eqout, size_t nquads, Ext ch, Ext* partial, unsigned* counter, Ext* result, unsigned long long* flag, unsigned long long seq) {
+  __shared__ Ext sm[TPB / 64];
+  Ext c[3] = {ex_zero(), ex_zero(), ex_zero()};
+  for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < nquads; q += (size_t)gridDim.x * blockDim.x) {
+    const Ext* pf = f + 4 * q; const Ext* pe = eq + 4 * q;
+    Ext a = ex_lerp(pf[0], pf[1], ch), a1 = ex_lerp(pf[2], pf[3], ch), ea = ex_lerp(pe[0], pe[1], ch), e1 = ex_lerp(pe[2], pe[3], ch);
+    fout[2 * q] = a; fout[2 * q + 1] = a1; eqout[2 * q] = ea; eqout[2 * q + 1] = e1;
+    bf_msg_acc(a, a1, ea, e1, c);
   }
-  size_t base = (size_t)blockIdx.x * 4;
-  Ext r;
-  r = block_reduce_ext(c0, sm); if (threadIdx.x == 0) partial[base] = r;
-  r = block_reduce_ext(c1, sm); if (threadIdx.x == 0) partial[base + 1] = r;
-  r = block_reduce_ext(c2, sm); if (threadIdx.x == 0) { partial[base + 2] = r; partial[base + 3] = ex_zero(); }
+  sc_block_sums_finish<3>(c, sm, partial, counter, result, flag, seq);
 }
 // K9: out[i] = y0 + (ch - x0)(y1 - y0) w,  x0 = gamma * w_{2^(level+1)}^{bitrev(i)},  w = -1/(2 x0)   (rs.rs:377-410)
 KBODY k_fri_fold(const Ext* in, Ext* out, size_t nout, unsigned level, const u64* tw, unsigned L, u64 gamma, u64 neg_inv2gamma, Ext ch) {
@@ -3283,13 +3295,11 @@ __device__ __forceinline__ void classic_fused_factored(const ClassicDesc& p, siz
   }
   c0 = ex_mul(c0, p.lo[0]); c2 = ex_mul(c2, p.lo[0]);
 }
-KBODY k_classic_fused(const unsigned* first, const ClassicDesc* d, int np, Ext r, int has_r, Ext* partial) {
-  __shared__ Ext sm[TPB / 64];
-  __shared__ int slot;
-  const int pi = seg_find(first, np, &slot);
+// this workgroup's share of its pair (`slot`: one int of LDS): the fold, and the thread's part of the two sums added to c0 / c2
+__device__ __forceinline__ void classic_fused_block(const unsigned* first, const ClassicDesc* d, int np, Ext r, int has_r, int* slot, Ext& c0, Ext& c2) {
+  const int pi = seg_find(first, np, slot);
   const ClassicDesc p = d[pi];
   const size_t b = blockIdx.x - first[pi], nb = first[pi + 1] - first[pi];
-  Ext c0 = ex_zero(), c2 = ex_zero();
   if (p.ln) classic_fused_factored(p, b, nb, r, has_r, c0, c2);
   else if (has_r && p.n > 1) {
     const size_t h = p.n / 2;  // length after the fold
@@ -3328,6 +3338,12 @@ KBODY k_classic_fused(const unsigned* first, const ClassicDesc* d, int np, Ext r
       }
     }
   }
+}
+KBODY k_classic_fused(const unsigned* first, const ClassicDesc* d, int np, Ext r, int has_r, Ext* partial) {
+  __shared__ Ext sm[TPB / 64];
+  __shared__ int slot;
+  Ext c0 = ex_zero(), c2 = ex_zero();
+  classic_fused_block(first, d, np, r, has_r, &slot, c0, c2);
   Ext t;
   t = block_reduce_ext(c0, sm); if (threadIdx.x == 0) partial[2 * (size_t)blockIdx.x] = t;
   t = block_reduce_ext(c2, sm); if (threadIdx.x == 0) partial[2 * (size_t)blockIdx.x + 1] = t;
@@ -3356,6 +3372,39 @@ KBODY k_classic_reduce(const unsigned* first, int np, const Ext* partial, Ext* r
   }
   __syncthreads();
   if (wave == 0) sc_publish_vals(result, res, 1, 2 * np, flag, seq, lane);
+}
+// k_classic_fused whose LAST workgroup is the round's k_classic_reduce (k_sc_fused's idiom: the two block sums written through, their acknowledgement
+// awaited, a relaxed ticket; whoever draws the last one reads every block sum past its L2, publishes and puts the ticket back to zero). `counter` is the
+// ticket of ONE proof: in a merged cohort launch every blockIdx.z brings its own (and its own result and flag), gridDim.x is the same for all of them.
+KBODY k_classic_fused_pub(const unsigned* first, const ClassicDesc* d, int np, Ext r, int has_r, Ext* partial, unsigned* counter, Ext* result, unsigned long long* flag, unsigned long long seq) {
+  __shared__ Ext sm[TPB / 64];
+  __shared__ int slot, s_last;
+  Ext c0 = ex_zero(), c2 = ex_zero();
+  classic_fused_block(first, d, np, r, has_r, &slot, c0, c2);
+  Ext t;
+  t = block_reduce_ext(c0, sm); if (threadIdx.x == 0) sc_store_through(&partial[2 * (size_t)blockIdx.x], t);
+  t = block_reduce_ext(c2, sm); if (threadIdx.x == 0) sc_store_through(&partial[2 * (size_t)blockIdx.x + 1], t);
+  if (threadIdx.x == 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    s_last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  DP_LDS_FRAME(Lds_k_classic_reduce, lf); auto& res = lf.res;
+  const int W = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int i = wave; i < np; i += W) {
+    Ext a0 = ex_zero(), a2 = ex_zero();
+    for (unsigned w = first[i] + lane; w < first[i + 1]; w += 64) {
+      const u64* pp = (const u64*)&partial[2 * (size_t)w];
+      a0 = ex_add(a0, ex(__hip_atomic_load(pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), __hip_atomic_load(pp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)));
+      a2 = ex_add(a2, ex(__hip_atomic_load(pp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), __hip_atomic_load(pp + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)));
+    }
+    a0 = wave_reduce_ext(a0); a2 = wave_reduce_ext(a2);
+    if (lane == 0) { res[2 * i] = a0; res[2 * i + 1] = a2; }
+  }
+  __syncthreads();
+  if (wave == 0) sc_publish_vals(result, res, 1, 2 * np, flag, seq, lane);
+  if (threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // the next launch on this stream starts from zero
 }
 struct EqDesc { Ext* out; unsigned k; unsigned pad; Ext pt[MAX_PT]; };
 // many eq tables in one launch: blockIdx.y selects the table (batch_open builds one per opened polynomial)
