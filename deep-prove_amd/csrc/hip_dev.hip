@@ -463,7 +463,6 @@ class HipDev : public Dev {
     nb_ = 0; DPL(k_publish, dim3(1), dim3(64), (const u64*)dres_, hres_dev_, (size_t)0, hflag_dev_, seq);
     wait_flag(seq, 0);
   }
-  // second stage of a block-partial reduction, published straight to hres_ (see k_reduce_publish); nout <= 1024
   // ---- sharded sumcheck with the shares on the device (Dev::ShareExchange)
   ShareExchange* share_x_ = nullptr; u64* dshare_ = nullptr; u64* dgather_ = nullptr; size_t dgather_words_ = 0;
   bool sc_set_share_exchange(ShareExchange* x) override {
@@ -484,6 +483,7 @@ class HipDev : public Dev {
     nb_ = 8.0 * (double)nwords * share_x_->world(); DPL(k_shares_sum_publish, dim3(1), dim3(256), (const u64*)dgather_, share_x_->world(), (int)(nwords / 2), (Ext*)hres_dev_, hflag_dev_, seq);
     wait_flag(seq, nwords);
   }
+  // second stage of a block-partial reduction, published straight to hres_ (see k_reduce_publish); nout <= 1024
   void reduce_publish(const Ext* partial, size_t nblocks, size_t inner, int nout) {
     DP_REQUIRE(nout >= 1 && nout <= 1024 && (size_t)nout * 2 <= RES_WORDS, DP_ERR_SHAPE, "reduce_publish: too many outputs");
     if (share_x_) {  // the reduction lands in device memory (the tag word too: nobody reads it), the exchange brings the ranks' total to hres_
@@ -505,6 +505,20 @@ class HipDev : public Dev {
     DPL(k_reduce_publish, dim3(1), dim3(threads), partial, nblocks, inner, nout, (Ext*)hres_dev_, hflag_dev_, seq);
     wait_flag(seq, (size_t)nout * 2);
   }
+  // The sums of a streamed round, after its launch: `published` — the launch's last workgroup (or a reduction the caller has launched) publishes `nout` values under
+  // `seq`; otherwise k_reduce_publish adds up the g x inner block sums of `partial`. Either way hres_ then holds them, and the first `nread` go to `out`.
+  void round_sums(bool published, unsigned long long seq, const Ext* partial, int g, size_t inner, int nout, Ext* out, int nread) {
+    if (published) wait_flag(seq, (size_t)nout * 2); else reduce_publish(partial, (size_t)g, inner, nout);
+    for (int i = 0; i < nread; i++) out[i] = ex(hres_[2 * i], hres_[2 * i + 1]);
+  }
+  // May the last workgroup of a streaming round kernel publish the round's sums, with fused_ticket_ as its ticket (kernels.inc, the last-workgroup epilogue)? Not with
+  // the sums on other ranks (share_x_) or without zero-copy results. Each family of kernels has its knob (read once); 0 brings back its separate reduction launches
+  // (DP_SC_GRID2=0: the round-by-round form of the first two rounds).
+  enum TicketKnob { TK_FUSED, TK_GRID2, TK_CLASSIC };
+  static bool ticket_knob(TicketKnob k) { static const bool on[3] = {knob("DP_FUSED_TICKET", 1) != 0, knob("DP_SC_GRID2", 1) != 0, knob("DP_CLASSIC_TICKET", 1) != 0}; return on[k]; }
+  // `in_cohorts`: members of a cohort too. A merged launch does not mix proofs (each blockIdx.z has its own pack, hence its own ticket, result and flag: classic_round
+  // and bf_round publish this way inside cohorts); sc_round passes false only because no test drives a sumcheck of its size through a cohort yet.
+  bool round_ticket_now(TicketKnob k, bool in_cohorts) const { return ticket_knob(k) && zerocopy_ && !share_x_ && fused_ticket_ != nullptr && (in_cohorts || !queued_()); }
   // bring `nwords` of dres_ to hres_
   void fetch(size_t nwords) {
     DP_REQUIRE(nwords <= RES_WORDS, DP_ERR_ARG, "result too large");
@@ -1472,15 +1486,13 @@ class HipDev : public Dev {
                                  else DPL_B((k_sc_fused2<KK, false>), 256, KF_NONE, dim3(g), dim3(TPB), 0, in[0], in[1], in[2], outp[0], outp[1], outp[2], nocts, grid2_.r1, *r, partial, fused_ticket_, (Ext*)hres_dev_, hflag_dev_, fseq); } while (0)
       if (nt == 1) LAUNCH_F2(1); else if (nt == 2) LAUNCH_F2(2); else LAUNCH_F2(3);
       #undef LAUNCH_F2
-      wait_flag(fseq, 8);
-      for (int t = 0; t <= K; t++) out[t] = ex(hres_[2 * t], hres_[2 * t + 1]);
+      round_sums(true, fseq, partial, g, 4, 4, out, K + 1);
       if (skip1) out[1] = ex_sub(*claim_hint_, out[0]);  // s(0) + s(1) = claim, exactly
       release(mk);
       return;
     }
     {
-      static const bool grid2_env = !(getenv("DP_SC_GRID2") && !atoi(getenv("DP_SC_GRID2")));
-      bool take = grid2_env && !r && !throughput_mode_ && !share_x_ && zerocopy_ && !queued_() && fused_ticket_ != nullptr && !sess_.active && !pend_eq_.p
+      bool take = round_ticket_now(TK_GRID2, false) && !r && !throughput_mode_ && !sess_.active && !pend_eq_.p
                   && nterms == 1 && terms[0].k == nt && nt <= 3 && n_in >= GRID2_MIN_N;
       for (int i = 0; take && i < nt; i++) { take = !tabs[i].ext; for (int j = 0; j < i; j++) take = take && terms[0].t[i] != terms[0].t[j]; }
       if (take) {
@@ -1496,8 +1508,8 @@ class HipDev : public Dev {
         if (nt == 1) DPL_B((k_sc_terms2<1>), 256, KF_NONE, dim3(g), dim3(TPB), 0, in[0], in[1], in[2], nquads, partial, fused_ticket_, (Ext*)hres_dev_, hflag_dev_, fseq);
         else if (nt == 2) DPL_B((k_sc_terms2<2>), 256, KF_NONE, dim3(g), dim3(TPB), 0, in[0], in[1], in[2], nquads, partial, fused_ticket_, (Ext*)hres_dev_, hflag_dev_, fseq);
         else DPL_B((k_sc_terms2<3>), 256, KF_NONE, dim3(g), dim3(TPB), 0, in[0], in[1], in[2], nquads, partial, fused_ticket_, (Ext*)hres_dev_, hflag_dev_, fseq);
-        wait_flag(fseq, 16);
-        for (int i = 0; i < 16; i++) grid2_.A[i] = hres_[i];
+        round_sums(true, fseq, partial, g, 8, 8, nullptr, 0);
+        for (int i = 0; i < 16; i++) grid2_.A[i] = hres_[i];  // (sixteen base-field sums)
         release(mk);
         {  // s1(t) = Q(t, 0) + Q(t, 1): the two polynomials in X1 from their values at 0, 1, -1 and their leading coefficients
           Ext c0[4], c1[4];
@@ -1658,14 +1670,10 @@ class HipDev : public Dev {
         Ext* partial = (Ext*)arena_alloc((size_t)g * 4 * 16);
         nb_ = bytes;
         const bool skip1 = claim_hint_ != nullptr;
-        // one proof on the GPU: the kernel's last workgroup reduces and publishes (no second launch). Cohort members still keep the separate
-        // reduction HERE — not because a merged launch mixes proofs (each blockIdx.z has its own pack, hence its own ticket, result and flag: classic_round
-        // and bf_round publish this way inside cohorts), but because no test drives a sumcheck of this size through a cohort yet.
+        // one proof on the GPU: the kernel's last workgroup reduces and publishes (no second launch); cohort members keep the separate reduction (round_ticket_now).
         // (round 2 had this OFF: its agent-scope release fence per workgroup wrote the XCD's whole L2 back 4096 times per launch, 162 / 40 us -> 1122 / 230 us.
-        // Round 4 publishes the 64 bytes of block sums write-through instead — kernels.inc, k_sc_fused — and it is the default; DP_FUSED_TICKET=0 restores the
-        // separate 14 us reduction launch per round.)
-        static const bool ticket_env = !(getenv("DP_FUSED_TICKET") && !atoi(getenv("DP_FUSED_TICKET")));
-        const bool inkernel = ticket_env && zerocopy_ && !queued_() && !share_x_ && fused_ticket_ != nullptr;
+        // Round 4 publishes the 64 bytes of block sums write-through instead and it is the default; DP_FUSED_TICKET=0 restores the separate 14 us reduction launch per round.)
+        const bool inkernel = round_ticket_now(TK_FUSED, false);
         unsigned* tick = inkernel ? fused_ticket_ : nullptr;
         const unsigned long long fseq = inkernel ? ++seq_ : 0;
         #define LAUNCH_FUSED2(KK, BB) do { if (skip1) DPL_B((k_sc_fused<KK, BB, true>), 256, KF_NONE, dim3(g), dim3(TPB), 0, in[0], in[1], in[2], outp[0], outp[1], outp[2], nquads, *r, partial, tick, (Ext*)hres_dev_, hflag_dev_, fseq); \
@@ -1674,8 +1682,7 @@ class HipDev : public Dev {
         if (nt == 1) LAUNCH_FUSED(1); else if (nt == 2) LAUNCH_FUSED(2); else LAUNCH_FUSED(3);
         #undef LAUNCH_FUSED
         #undef LAUNCH_FUSED2
-        if (inkernel) wait_flag(fseq, 8); else reduce_publish(partial, (size_t)g, 4, 4);
-        for (int t = 0; t <= terms[0].k; t++) out[t] = ex(hres_[2 * t], hres_[2 * t + 1]);
+        round_sums(inkernel, fseq, partial, g, 4, 4, out, terms[0].k + 1);
         if (skip1) out[1] = ex_sub(*claim_hint_, out[0]);  // s(0) + s(1) = claim, exactly
         release(mk);
         return;
@@ -2051,15 +2058,8 @@ class HipDev : public Dev {
     }
     nb_ = bytes; DPL(k_eq_outer_many, dim3(grid_for(maxn, 64), (unsigned)n), dim3(TPB), dd);
   }
-  // The rounds of the batch opening (classic_round, bf_round) publish from the last workgroup of their streaming kernel, with fused_ticket_ as the ticket.
-  // ONE ticket word per context is enough: every kernel that takes tickets is followed by the host's wait for what it publishes before the context launches
-  // anything else, a context launches on one stream (its own, or its cohort's, where its packs of two launches never share a launch), and the last workgroup
-  // writes the zero back before the kernel ends. Not with the sums on other ranks (share_x_) or without zero-copy results. DP_CLASSIC_TICKET=0 (read once):
-  // the separate reduction launches.
-  bool round_ticket_now() const {
-    static const bool env = knob("DP_CLASSIC_TICKET", 1) != 0;
-    return env && zerocopy_ && !share_x_ && fused_ticket_ != nullptr;
-  }
+  // The rounds of the batch opening (classic_round, bf_round) publish from the last workgroup of their streaming kernel, members of a cohort included
+  // (round_ticket_now). DP_CLASSIC_TICKET=0: the separate reduction launches.
   void classic_round(DBuf* fs, DBuf* eqs, DBuf* los, int np, const Ext* r, Ext* out) override {
     DP_REQUIRE((size_t)np * (sizeof(PolyDesc) * 2 + sizeof(ClassicDesc) + 4) + 320 <= DESC_BYTES && (size_t)np * 4 <= RES_WORDS && np * 2 <= 1024, DP_ERR_SHAPE, "classic_round: too many polynomials");
     if (desc_off_ + (size_t)np * (sizeof(PolyDesc) * 2 + sizeof(ClassicDesc) + 4) + 320 > DESC_BYTES) stream_wait();
@@ -2106,13 +2106,12 @@ class HipDev : public Dev {
       DP_REQUIRE(2 * np <= REDUCE_LDS_VALUES, DP_ERR_SHAPE, "classic round: too many polynomials for one reduction");
       // the last workgroup of the fused launch reduces and publishes (k_classic_fused_pub), members of a cohort included: a member brings its own ticket,
       // result and flag in its argument pack. DP_CLASSIC_TICKET=0: the separate one-workgroup reduction launch per round, as before.
-      if (round_ticket_now()) { nb_ = bytes; DPL(k_classic_fused_pub, dim3(nblk), dim3(TPB), fd, cdd, np, r ? *r : ex_zero(), r ? 1 : 0, partial, fused_ticket_, (Ext*)hres_dev_, hflag_dev_, seq); }
+      if (round_ticket_now(TK_CLASSIC, true)) { nb_ = bytes; DPL(k_classic_fused_pub, dim3(nblk), dim3(TPB), fd, cdd, np, r ? *r : ex_zero(), r ? 1 : 0, partial, fused_ticket_, (Ext*)hres_dev_, hflag_dev_, seq); }
       else {
         nb_ = bytes; DPL(k_classic_fused, dim3(nblk), dim3(TPB), fd, cdd, np, r ? *r : ex_zero(), r ? 1 : 0, partial);
         nb_ = 0; DPL(k_classic_reduce, dim3(1), dim3(np >= 8 && !throughput_mode_ ? 1024 : 256), fd, np, (const Ext*)partial, (Ext*)hres_dev_, hflag_dev_, seq);
       }
-      wait_flag(seq, (size_t)np * 4);
-      for (int i = 0; i < 2 * np; i++) out[i] = ex(hres_[2 * i], hres_[2 * i + 1]);
+      round_sums(true, seq, partial, (int)nblk, 2, 2 * np, out, 2 * np);
       release(mk);
       return;
     }
@@ -2156,7 +2155,7 @@ class HipDev : public Dev {
   }
   void bf_round(DBuf& eq, DBuf& f, const Ext* ch, Ext* msg) override {
     DP_REQUIRE(eq.ext && f.ext && eq.n == f.n, DP_ERR_SHAPE, "bf_round: shapes");
-    const bool pub = round_ticket_now();
+    const bool pub = round_ticket_now(TK_CLASSIC, true);
     if (ch && msg && pub && f.n > 2 && f.n % 4 == 0) {
       // fold and message in one pass over eq and f, published by the kernel's last workgroup (k_bf_fold_msg): one launch before the wait instead of three
       DBuf fo = alloc(f.n / 2, true), eo = alloc(eq.n / 2, true);
@@ -2166,8 +2165,7 @@ class HipDev : public Dev {
       Ext* partial = (Ext*)arena_alloc((size_t)g * 3 * 16);
       unsigned long long seq = ++seq_;
       nb_ = 48.0 * f.n; DPL(k_bf_fold_msg, dim3(g), dim3(TPB), (const Ext*)f.p, (const Ext*)eq.p, (Ext*)fo.p, (Ext*)eo.p, nquads, *ch, partial, fused_ticket_, (Ext*)hres_dev_, hflag_dev_, seq);
-      wait_flag(seq, 6);
-      for (int i = 0; i < 3; i++) msg[i] = ex(hres_[2 * i], hres_[2 * i + 1]);
+      round_sums(true, seq, partial, g, 3, 3, msg, 3);
       release(mk);
       f = fo; eq = eo;
       return;
@@ -2180,8 +2178,7 @@ class HipDev : public Dev {
     Ext* partial = (Ext*)arena_alloc((size_t)g * 3 * 16);
     unsigned long long seq = pub ? ++seq_ : 0;
     nb_ = 32.0 * f.n; DPL(k_bf_msg, dim3(g), dim3(TPB), (const Ext*)f.p, (const Ext*)eq.p, f.n / 2, partial, pub ? fused_ticket_ : (unsigned*)nullptr, (Ext*)hres_dev_, hflag_dev_, seq);
-    if (pub) wait_flag(seq, 6); else reduce_publish(partial, (size_t)g, 3, 3);
-    for (int i = 0; i < 3; i++) msg[i] = ex(hres_[2 * i], hres_[2 * i + 1]);
+    round_sums(pub, seq, partial, g, 3, 3, msg, 3);
     release(mk);
   }
   DBuf fri_fold(const DBuf& o, unsigned level, Ext ch) override {

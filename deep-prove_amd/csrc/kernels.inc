@@ -391,13 +391,76 @@ KBODY k_reduce_terms(const Ext* partial, size_t nblocks, Ext* out) {
 // table a second time). partial[block*4 + t] = sum over the block's pairs of prod_j (f0_j + t (f1_j - f0_j)).
 // SKIP1: the caller knows the round's claimed sum s(0) + s(1), so the t = 1 products are not computed (slot 1 stays 0
 // and the host sets s(1) = claim - s(0)): 2 of the 8 extension products per pair less.
-// `counter` non-null: the LAST workgroup to finish (a device-wide ticket) adds up the partials of all workgroups and publishes
-// the four sums to the host itself — no k_reduce_publish launch between two rounds of a large sumcheck. The partials cross
-// XCDs (per-XCD L2s are not coherent with each other): every workgroup releases at agent scope before it takes its ticket, the
-// last one acquires at agent scope before it reads (MI355X_MICROARCH.md, correctness boundaries).
+// `counter` non-null: the last workgroup to finish adds up the block sums of all workgroups and publishes the four sums to the host itself — no k_reduce_publish
+// launch between two rounds of a large sumcheck (the last-workgroup epilogue below).
 __device__ void sc_publish_vals_fwd(Ext* result, const Ext* src, size_t stride, int n, unsigned long long* flag, unsigned long long seq, int lane);
-__device__ __forceinline__ void sc_store_through(Ext* p, Ext v) {  // written through every cache level (system-scope relaxed stores)
+// ---- the last-workgroup epilogue of the streaming round kernels (k_sc_fused, k_sc_terms2, k_sc_fused2, k_bf_msg, k_bf_fold_msg: sc_block_sums_finish; k_classic_fused_pub)
+// Every workgroup stores its block sums, then takes a ticket; whoever draws the last one adds all block sums up, publishes the round's sums to the host and puts the
+// ticket back to zero. The block sums must reach that workgroup — possibly on another XCD, behind another L2, and the per-XCD L2s are not coherent with each other.
+//  * Written through, not fenced: an agent-scope release fence per workgroup writes the XCD's whole L2 back (the folded tables the kernel has just written), thousands of
+//    times per launch — 7x slower than a second launch. Instead the few block sums are WRITTEN THROUGH every cache level (system-scope relaxed stores, the idiom of every
+//    host publication of this file), thread 0 waits for their acknowledgement (gfx9 counts stores in vmcnt) and only then takes the ticket, a relaxed memory-side atomic.
+//  * The last workgroup reads every block sum PAST its own L2 (system-scope relaxed loads): no acquire fence, no invalidation of the bulk data. This rests on how the
+//    caches treat system-scope accesses, which the HIP memory model does not spell out (tests/test_gpu_sharded.py, the ticket test, says what is relied on).
+//  * ONE ticket word per context is enough: the host waits for what such a kernel publishes before the context launches anything else, a context launches on one
+//    stream (its own, or its cohort's, where every blockIdx.z brings its own ticket, result and flag), and the zero is written back before the kernel ends.
+__device__ __forceinline__ void sc_store_through(Ext* p, Ext v) {
   __hip_atomic_store((u64*)p, v.c0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); __hip_atomic_store((u64*)p + 1, v.c1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__device__ __forceinline__ bool sums_ticket_take(unsigned* counter) {  // after thread 0's sc_store_through calls; true in every thread of the workgroup that drew the last ticket
+  __shared__ int s_last;
+  if (threadIdx.x == 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    s_last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+  }
+  __syncthreads();
+  return s_last;
+}
+__device__ __forceinline__ Ext ld_through(const Ext* p) {
+  return ex(__hip_atomic_load((const u64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), __hip_atomic_load((const u64*)p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+}
+__device__ __forceinline__ void sums_ticket_return(unsigned* counter) {  // one thread, after the publication: the next launch of this context starts from zero
+  __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// partial[NV * block + i] = the block's sum of vals[i]; `counter` non-null: the epilogue above, the NV sums published to `result` under `seq`
+template <int NV>
+__device__ __forceinline__ void sc_block_sums_finish(const Ext* vals, Ext* sm, Ext* partial, unsigned* counter, Ext* result, unsigned long long* flag, unsigned long long seq) {
+  const size_t base = (size_t)blockIdx.x * NV;
+  if (counter) {
+#pragma unroll
+    for (int i = 0; i < NV; i++) { Ext v = block_reduce_ext(vals[i], sm); if (threadIdx.x == 0) sc_store_through(&partial[base + i], v); }
+    __shared__ Ext res[NV];
+    if (sums_ticket_take(counter)) {
+      const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nwaves = blockDim.x >> 6;
+      for (int i = wave; i < NV; i += nwaves) {
+        Ext acc = ex_zero();
+        for (unsigned b = lane; b < gridDim.x; b += 64) acc = ex_add(acc, ld_through(&partial[(size_t)b * NV + i]));
+        acc = wave_reduce_ext(acc);
+        if (lane == 0) res[i] = acc;
+      }
+      __syncthreads();
+      if (wave == 0) sc_publish_vals_fwd(result, res, 1, NV, flag, seq, lane);
+      if (threadIdx.x == 0) sums_ticket_return(counter);
+    }
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < NV; i++) { Ext v = block_reduce_ext(vals[i], sm); if (threadIdx.x == 0) partial[base + i] = v; }
+}
+// the round sums of one folded pair of K tables: acc_t += prod_j (f0_j + t (f1_j - f0_j)), t = 0 .. K (t = 1 left out with SKIP1), shared by k_sc_fused and k_sc_fused2
+template <int K, bool SKIP1>
+__device__ __forceinline__ void sc_prod_acc(const Ext (&f0)[K], const Ext (&f1)[K], lz::ExAcc& acc0, lz::ExAcc& acc1, lz::ExAcc& acc2, lz::ExAcc& acc3) {
+  if (K == 1) { lz::acc_add(acc0, f0[0]); if (!SKIP1) lz::acc_add(acc1, f1[0]); }
+  else if (K == 2) {
+    Ext c0 = ex_sub(ex_dbl(f1[0]), f0[0]), c1 = ex_sub(ex_dbl(f1[1]), f0[1]);
+    lz::acc_add(acc0, lz::ex_mul(f0[0], f0[1])); if (!SKIP1) lz::acc_add(acc1, lz::ex_mul(f1[0], f1[1])); lz::acc_add(acc2, lz::ex_mul(c0, c1));
+  } else {
+    Ext d0 = ex_sub(f1[0], f0[0]), d1 = ex_sub(f1[1], f0[1]), d2 = ex_sub(f1[2], f0[2]);
+    Ext c0 = ex_add(f1[0], d0), c1 = ex_add(f1[1], d1), c2 = ex_add(f1[2], d2);
+    Ext g0 = ex_add(c0, d0), g1 = ex_add(c1, d1), g2 = ex_add(c2, d2);
+    lz::acc_add(acc0, lz::ex_mul(lz::ex_mul(f0[0], f0[1]), f0[2])); if (!SKIP1) lz::acc_add(acc1, lz::ex_mul(lz::ex_mul(f1[0], f1[1]), f1[2]));
+    lz::acc_add(acc2, lz::ex_mul(lz::ex_mul(c0, c1), c2)); lz::acc_add(acc3, lz::ex_mul(lz::ex_mul(g0, g1), g2));
+  }
 }
 template <int K, bool BASE, bool SKIP1>
 KBODY k_sc_fused(const void* in0, const void* in1, const void* in2, Ext* out0, Ext* out1, Ext* out2,
@@ -428,58 +491,10 @@ KBODY k_sc_fused(const void* in0, const void* in1, const void* in2, Ext* out0, E
       out[j][2 * q] = f0[j];
       out[j][2 * q + 1] = f1[j];
     }
-    if (K == 1) { lz::acc_add(acc0, f0[0]); if (!SKIP1) lz::acc_add(acc1, f1[0]); }
-    else if (K == 2) {
-      Ext c0 = ex_sub(ex_dbl(f1[0]), f0[0]), c1 = ex_sub(ex_dbl(f1[1]), f0[1]);
-      lz::acc_add(acc0, lz::ex_mul(f0[0], f0[1])); if (!SKIP1) lz::acc_add(acc1, lz::ex_mul(f1[0], f1[1])); lz::acc_add(acc2, lz::ex_mul(c0, c1));
-    } else {
-      Ext d0 = ex_sub(f1[0], f0[0]), d1 = ex_sub(f1[1], f0[1]), d2 = ex_sub(f1[2], f0[2]);
-      Ext c0 = ex_add(f1[0], d0), c1 = ex_add(f1[1], d1), c2 = ex_add(f1[2], d2);
-      Ext g0 = ex_add(c0, d0), g1 = ex_add(c1, d1), g2 = ex_add(c2, d2);
-      lz::acc_add(acc0, lz::ex_mul(lz::ex_mul(f0[0], f0[1]), f0[2])); if (!SKIP1) lz::acc_add(acc1, lz::ex_mul(lz::ex_mul(f1[0], f1[1]), f1[2]));
-      lz::acc_add(acc2, lz::ex_mul(lz::ex_mul(c0, c1), c2)); lz::acc_add(acc3, lz::ex_mul(lz::ex_mul(g0, g1), g2));
-    }
+    sc_prod_acc<K, SKIP1>(f0, f1, acc0, acc1, acc2, acc3);
   }
-  size_t base = (size_t)blockIdx.x * 4;
-  Ext v;
-  // With a ticket (one proof on the GPU) the block sums must reach the workgroup that takes the last ticket — possibly on another XCD, behind another L2.
-  // Round 2 ordered that with an agent-scope release fence per workgroup: a write-back of the XCD's whole L2 (the folded tables this kernel has just
-  // written) 4096 times per launch, 7x slower than a second launch. Round 4: the 64 bytes of block sums are WRITTEN THROUGH (system-scope relaxed stores, the
-  // same idiom as every host publication of this file), the workgroup waits for their acknowledgement (s_waitcnt vmcnt(0)) and only then takes its ticket
-  // (a memory-side atomic); the last workgroup reads all block sums past its own L2 (system-scope loads). No fence, no write-back of the bulk data.
-  if (counter) {
-    v = block_reduce_ext(lz::acc_value(acc0), sm); if (threadIdx.x == 0) { sc_store_through(&partial[base + 0], v); }
-    v = block_reduce_ext(lz::acc_value(acc1), sm); if (threadIdx.x == 0) { sc_store_through(&partial[base + 1], v); }
-    v = block_reduce_ext(lz::acc_value(acc2), sm); if (threadIdx.x == 0) { sc_store_through(&partial[base + 2], v); }
-    v = block_reduce_ext(lz::acc_value(acc3), sm); if (threadIdx.x == 0) { sc_store_through(&partial[base + 3], v); }
-    __shared__ int s_last;
-    __shared__ Ext res[4];
-    if (threadIdx.x == 0) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (gfx9 counts stores in vmcnt: the write-through stores above have been acknowledged)
-      s_last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (s_last) {
-      const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-      if (wave < 4) {
-        Ext acc = ex_zero();
-        for (unsigned b = lane; b < gridDim.x; b += 64) {
-          const u64* pp = (const u64*)&partial[(size_t)b * 4 + wave];
-          acc = ex_add(acc, ex(__hip_atomic_load(pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), __hip_atomic_load(pp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)));
-        }
-        acc = wave_reduce_ext(acc);
-        if (lane == 0) res[wave] = acc;
-      }
-      __syncthreads();
-      if (wave == 0) sc_publish_vals_fwd(result, res, 1, 4, flag, seq, lane);
-      if (threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // the next launch on this stream starts from zero
-    }
-    return;
-  }
-  v = block_reduce_ext(lz::acc_value(acc0), sm); if (threadIdx.x == 0) partial[base + 0] = v;
-  v = block_reduce_ext(lz::acc_value(acc1), sm); if (threadIdx.x == 0) partial[base + 1] = v;
-  v = block_reduce_ext(lz::acc_value(acc2), sm); if (threadIdx.x == 0) partial[base + 2] = v;
-  v = block_reduce_ext(lz::acc_value(acc3), sm); if (threadIdx.x == 0) partial[base + 3] = v;
+  Ext vals[4] = {lz::acc_value(acc0), lz::acc_value(acc1), lz::acc_value(acc2), lz::acc_value(acc3)};
+  sc_block_sums_finish<4>(vals, sm, partial, counter, result, flag, seq);
 }
 // ---- the first TWO rounds of one product of K base-field tables in one pass, and both folds in one pass (round 6; Dev::sc_round, "grid2")
 // Round 1 needs no challenge, and round 2's polynomial is a polynomial of degree K in the FIRST challenge: with f_j(X1, X2, x') the bilinear extension of a
@@ -489,39 +504,6 @@ KBODY k_sc_fused(const void* in0, const void* in1, const void* in2, Ext* out0, E
 // base tables are then read ONCE more: k_sc_fused2 folds both variables (f = e0 + r2 (e1 - e0), e = a + r1 (b - a)), writes tables a QUARTER as long and
 // sums round 3. Against k_sc_terms + two k_sc_fused launches that is 1.0 instead of 1.8 GB of traffic at 3 x 2^24 entries and one host round trip less.
 // The sixteen sums are base-field values; they travel as eight (c0, c1) pairs through the extension-field reductions (an extension addition is limb-wise).
-template <int NV>
-__device__ __forceinline__ void sc_block_sums_finish(const Ext* vals, Ext* sm, Ext* partial, unsigned* counter, Ext* result, unsigned long long* flag, unsigned long long seq) {
-  const size_t base = (size_t)blockIdx.x * NV;
-  if (counter) {  // (k_sc_fused's idiom: block sums written through, their acknowledgement awaited, a relaxed ticket; the last workgroup reads past its L2)
-#pragma unroll
-    for (int i = 0; i < NV; i++) { Ext v = block_reduce_ext(vals[i], sm); if (threadIdx.x == 0) sc_store_through(&partial[base + i], v); }
-    __shared__ int s_last;
-    __shared__ Ext res[NV];
-    if (threadIdx.x == 0) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      s_last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (s_last) {
-      const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nwaves = blockDim.x >> 6;
-      for (int i = wave; i < NV; i += nwaves) {
-        Ext acc = ex_zero();
-        for (unsigned b = lane; b < gridDim.x; b += 64) {
-          const u64* pp = (const u64*)&partial[(size_t)b * NV + i];
-          acc = ex_add(acc, ex(__hip_atomic_load(pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), __hip_atomic_load(pp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)));
-        }
-        acc = wave_reduce_ext(acc);
-        if (lane == 0) res[i] = acc;
-      }
-      __syncthreads();
-      if (wave == 0) sc_publish_vals_fwd(result, res, 1, NV, flag, seq, lane);
-      if (threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < NV; i++) { Ext v = block_reduce_ext(vals[i], sm); if (threadIdx.x == 0) partial[base + i] = v; }
-}
 // The grid is chip-sized (768 workgroups: three 140-register waves per SIMD, all resident at once) and every thread walks ~20 quads with the next quad's loads in
 // flight while it multiplies (~600 VALU instructions per quad: 32 multiplications of 12, 36 subtractions, 16 wide sums): with 4096 workgroups of 4 quads per thread
 // the eight block reductions cost a third of the work again and nothing covered the load latency — 199 us at 3 x 2^24 entries against 105 us for k_sc_terms.
@@ -593,17 +575,7 @@ KBODY k_sc_fused2(const void* in0, const void* in1, const void* in2, Ext* out0, 
       out[j][2 * q] = f0[j];
       out[j][2 * q + 1] = f1[j];
     }
-    if (K == 1) { lz::acc_add(acc0, f0[0]); if (!SKIP1) lz::acc_add(acc1, f1[0]); }
-    else if (K == 2) {
-      Ext c0 = ex_sub(ex_dbl(f1[0]), f0[0]), c1 = ex_sub(ex_dbl(f1[1]), f0[1]);
-      lz::acc_add(acc0, lz::ex_mul(f0[0], f0[1])); if (!SKIP1) lz::acc_add(acc1, lz::ex_mul(f1[0], f1[1])); lz::acc_add(acc2, lz::ex_mul(c0, c1));
-    } else {
-      Ext d0 = ex_sub(f1[0], f0[0]), d1 = ex_sub(f1[1], f0[1]), d2 = ex_sub(f1[2], f0[2]);
-      Ext c0 = ex_add(f1[0], d0), c1 = ex_add(f1[1], d1), c2 = ex_add(f1[2], d2);
-      Ext g0 = ex_add(c0, d0), g1 = ex_add(c1, d1), g2 = ex_add(c2, d2);
-      lz::acc_add(acc0, lz::ex_mul(lz::ex_mul(f0[0], f0[1]), f0[2])); if (!SKIP1) lz::acc_add(acc1, lz::ex_mul(lz::ex_mul(f1[0], f1[1]), f1[2]));
-      lz::acc_add(acc2, lz::ex_mul(lz::ex_mul(c0, c1), c2)); lz::acc_add(acc3, lz::ex_mul(lz::ex_mul(g0, g1), g2));
-    }
+    sc_prod_acc<K, SKIP1>(f0, f1, acc0, acc1, acc2, acc3);
   }
   Ext vals[4] = {lz::acc_value(acc0), lz::acc_value(acc1), lz::acc_value(acc2), lz::acc_value(acc3)};
   sc_block_sums_finish<4>(vals, sm, partial, counter, result, flag, seq);
@@ -799,6 +771,26 @@ KBODY k_classic_fold(const PolyDesc* d, Ext r) {
     else p.fout[i] = ex_lerp_base(((const u64*)p.f)[2 * i], ((const u64*)p.f)[2 * i + 1], r);
   }
 }
+// the classic round kernels (k_classic_sums, k_classic_fused): entries 4 j .. 4 j + 3 of f, base or extension, folded by r into two
+__device__ __forceinline__ void classic_fold_quad(const void* f, int fext, size_t j, Ext r, Ext& f0, Ext& f1) {
+  if (fext) { const Ext* q = (const Ext*)f + 4 * j; f0 = ex_lerp(q[0], q[1], r); f1 = ex_lerp(q[2], q[3], r); }
+  else { const u64* q = (const u64*)f + 4 * j; f0 = ex_lerp_base(q[0], q[1], r); f1 = ex_lerp_base(q[2], q[3], r); }
+}
+// c0 += sum f0 e0, c2 += sum (f1 - f0)(e1 - e0) over the pairs j = start, start + stride, .. < npairs of f and eq as they are stored
+__device__ __forceinline__ void classic_pair_sums(const void* f, int fext, const Ext* eq, size_t start, size_t stride, size_t npairs, Ext& c0, Ext& c2) {
+  for (size_t j = start; j < npairs; j += stride) {
+    Ext l0 = eq[2 * j], l1 = eq[2 * j + 1];
+    if (fext) {
+      Ext r0 = ((const Ext*)f)[2 * j], r1 = ((const Ext*)f)[2 * j + 1];
+      c0 = ex_add(c0, ex_mul(l0, r0));
+      c2 = ex_add(c2, ex_mul(ex_sub(l1, l0), ex_sub(r1, r0)));
+    } else {
+      u64 r0 = ((const u64*)f)[2 * j], r1 = ((const u64*)f)[2 * j + 1];
+      c0 = ex_add(c0, ex_mul_base(l0, r0));
+      c2 = ex_add(c2, ex_mul_base(ex_sub(l1, l0), gl_sub(r1, r0)));
+    }
+  }
+}
 // partial[(poly*gridDim.x + block)*2 + {0,1}]: c0 = sum f0*e0, c2 = sum (f1-f0)(e1-e0)   (coeff.rs:236-345)
 KBODY k_classic_sums(const PolyDesc* d, Ext* partial) {
   __shared__ Ext sm[TPB / 64];
@@ -806,21 +798,7 @@ KBODY k_classic_sums(const PolyDesc* d, Ext* partial) {
   Ext c0 = ex_zero(), c2 = ex_zero();
   if (p.n == 1) {
     if (blockIdx.x == 0 && threadIdx.x == 0) c0 = ex_mul(ld_elem(p.f, p.fext, 0), p.eq[0]);
-  } else {
-    size_t h = p.n / 2;
-    for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < h; j += (size_t)gridDim.x * blockDim.x) {
-      Ext l0 = p.eq[2 * j], l1 = p.eq[2 * j + 1];
-      if (p.fext) {
-        Ext r0 = ((const Ext*)p.f)[2 * j], r1 = ((const Ext*)p.f)[2 * j + 1];
-        c0 = ex_add(c0, ex_mul(l0, r0));
-        c2 = ex_add(c2, ex_mul(ex_sub(l1, l0), ex_sub(r1, r0)));
-      } else {
-        u64 r0 = ((const u64*)p.f)[2 * j], r1 = ((const u64*)p.f)[2 * j + 1];
-        c0 = ex_add(c0, ex_mul_base(l0, r0));
-        c2 = ex_add(c2, ex_mul_base(ex_sub(l1, l0), gl_sub(r1, r0)));
-      }
-    }
-  }
+  } else classic_pair_sums(p.f, p.fext, p.eq, blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, p.n / 2, c0, c2);
   size_t base = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
   Ext r;
   r = block_reduce_ext(c0, sm); if (threadIdx.x == 0) partial[base] = r;
@@ -3229,8 +3207,7 @@ __device__ __forceinline__ void classic_fused_factored(const ClassicDesc& p, siz
       if (b == 0) for (unsigned q = threadIdx.x; q < ln / 2; q += blockDim.x) p.loout[q] = ex_lerp(p.lo[2 * q], p.lo[2 * q + 1], r);
       for (size_t j = b * blockDim.x + threadIdx.x; j < h / 2; j += nb * blockDim.x) {
         Ext f0, f1;
-        if (p.fext) { const Ext* q = (const Ext*)p.f + 4 * j; f0 = ex_lerp(q[0], q[1], r); f1 = ex_lerp(q[2], q[3], r); }
-        else { const u64* q = (const u64*)p.f + 4 * j; f0 = ex_lerp_base(q[0], q[1], r); f1 = ex_lerp_base(q[2], q[3], r); }
+        classic_fold_quad(p.f, p.fext, j, r, f0, f1);
         p.fout[2 * j] = f0; p.fout[2 * j + 1] = f1;
         const Ext* ql = p.lo + ((4 * j) & (ln - 1));
         const Ext H = p.eq[(4 * j) >> llog];
@@ -3249,8 +3226,7 @@ __device__ __forceinline__ void classic_fused_factored(const ClassicDesc& p, siz
     } else s = p.lo[0];
     for (size_t j = b * blockDim.x + threadIdx.x; j < h / 2; j += nb * blockDim.x) {
       Ext f0, f1;
-      if (p.fext) { const Ext* q = (const Ext*)p.f + 4 * j; f0 = ex_lerp(q[0], q[1], r); f1 = ex_lerp(q[2], q[3], r); }
-      else { const u64* q = (const u64*)p.f + 4 * j; f0 = ex_lerp_base(q[0], q[1], r); f1 = ex_lerp_base(q[2], q[3], r); }
+      classic_fold_quad(p.f, p.fext, j, r, f0, f1);
       p.fout[2 * j] = f0; p.fout[2 * j + 1] = f1;
       Ext e0, e1;
       if (ln == 2) { e0 = p.eq[2 * j]; e1 = p.eq[2 * j + 1]; }
@@ -3281,18 +3257,7 @@ __device__ __forceinline__ void classic_fused_factored(const ClassicDesc& p, siz
     }
     return;
   }
-  for (size_t j = b * blockDim.x + threadIdx.x; j < p.n / 2; j += nb * blockDim.x) {
-    Ext l0 = p.eq[2 * j], l1 = p.eq[2 * j + 1];
-    if (p.fext) {
-      Ext r0 = ((const Ext*)p.f)[2 * j], r1 = ((const Ext*)p.f)[2 * j + 1];
-      c0 = ex_add(c0, ex_mul(l0, r0));
-      c2 = ex_add(c2, ex_mul(ex_sub(l1, l0), ex_sub(r1, r0)));
-    } else {
-      u64 r0 = ((const u64*)p.f)[2 * j], r1 = ((const u64*)p.f)[2 * j + 1];
-      c0 = ex_add(c0, ex_mul_base(l0, r0));
-      c2 = ex_add(c2, ex_mul_base(ex_sub(l1, l0), gl_sub(r1, r0)));
-    }
-  }
+  classic_pair_sums(p.f, p.fext, p.eq, b * blockDim.x + threadIdx.x, nb * blockDim.x, p.n / 2, c0, c2);  // ln == 1: the sums are linear in the scalar lo[0], which multiplies them once
   c0 = ex_mul(c0, p.lo[0]); c2 = ex_mul(c2, p.lo[0]);
 }
 // this workgroup's share of its pair (`slot`: one int of LDS): the fold, and the thread's part of the two sums added to c0 / c2
@@ -3313,8 +3278,7 @@ __device__ __forceinline__ void classic_fused_block(const unsigned* first, const
     } else {
       for (size_t j = b * blockDim.x + threadIdx.x; j < h / 2; j += nb * blockDim.x) {
         Ext f0, f1;
-        if (p.fext) { const Ext* q = (const Ext*)p.f + 4 * j; f0 = ex_lerp(q[0], q[1], r); f1 = ex_lerp(q[2], q[3], r); }
-        else { const u64* q = (const u64*)p.f + 4 * j; f0 = ex_lerp_base(q[0], q[1], r); f1 = ex_lerp_base(q[2], q[3], r); }
+        classic_fold_quad(p.f, p.fext, j, r, f0, f1);
         const Ext* qe = p.eq + 4 * j;
         Ext e0 = ex_lerp(qe[0], qe[1], r), e1 = ex_lerp(qe[2], qe[3], r);
         p.fout[2 * j] = f0; p.fout[2 * j + 1] = f1; p.eqout[2 * j] = e0; p.eqout[2 * j + 1] = e1;
@@ -3324,20 +3288,7 @@ __device__ __forceinline__ void classic_fused_block(const unsigned* first, const
     }
   } else if (p.n == 1) {
     if (b == 0 && threadIdx.x == 0) c0 = ex_mul(ld_elem(p.f, p.fext, 0), p.eq[0]);
-  } else {
-    for (size_t j = b * blockDim.x + threadIdx.x; j < p.n / 2; j += nb * blockDim.x) {
-      Ext l0 = p.eq[2 * j], l1 = p.eq[2 * j + 1];
-      if (p.fext) {
-        Ext r0 = ((const Ext*)p.f)[2 * j], r1 = ((const Ext*)p.f)[2 * j + 1];
-        c0 = ex_add(c0, ex_mul(l0, r0));
-        c2 = ex_add(c2, ex_mul(ex_sub(l1, l0), ex_sub(r1, r0)));
-      } else {
-        u64 r0 = ((const u64*)p.f)[2 * j], r1 = ((const u64*)p.f)[2 * j + 1];
-        c0 = ex_add(c0, ex_mul_base(l0, r0));
-        c2 = ex_add(c2, ex_mul_base(ex_sub(l1, l0), gl_sub(r1, r0)));
-      }
-    }
-  }
+  } else classic_pair_sums(p.f, p.fext, p.eq, b * blockDim.x + threadIdx.x, nb * blockDim.x, p.n / 2, c0, c2);
 }
 KBODY k_classic_fused(const unsigned* first, const ClassicDesc* d, int np, Ext r, int has_r, Ext* partial) {
   __shared__ Ext sm[TPB / 64];
@@ -3361,50 +3312,37 @@ KBODY k_eq_outer_many(const EqOuterDesc* d) {
 struct Lds_k_classic_reduce {
   Ext res[REDUCE_LDS_VALUES];
 };
-KBODY k_classic_reduce(const unsigned* first, int np, const Ext* partial, Ext* result, unsigned long long* flag, unsigned long long seq) {
-  DP_LDS_FRAME(Lds_k_classic_reduce, lf); auto& res = lf.res;
-  int tid = threadIdx.x, W = blockDim.x >> 6, wave = tid >> 6, lane = tid & 63;
+// one workgroup adds up the workgroups of each pair (wave w owns pairs w, w + W, ..) and publishes; `ld` loads one block sum
+template <class Load>
+__device__ __forceinline__ void classic_reduce_pairs(const unsigned* first, int np, const Ext* partial, Ext* res, Ext* result, unsigned long long* flag, unsigned long long seq, Load ld) {
+  const int W = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int i = wave; i < np; i += W) {
     Ext a0 = ex_zero(), a2 = ex_zero();
-    for (unsigned w = first[i] + lane; w < first[i + 1]; w += 64) { a0 = ex_add(a0, partial[2 * (size_t)w]); a2 = ex_add(a2, partial[2 * (size_t)w + 1]); }
+    for (unsigned w = first[i] + lane; w < first[i + 1]; w += 64) { a0 = ex_add(a0, ld(&partial[2 * (size_t)w])); a2 = ex_add(a2, ld(&partial[2 * (size_t)w + 1])); }
     a0 = wave_reduce_ext(a0); a2 = wave_reduce_ext(a2);
     if (lane == 0) { res[2 * i] = a0; res[2 * i + 1] = a2; }
   }
   __syncthreads();
   if (wave == 0) sc_publish_vals(result, res, 1, 2 * np, flag, seq, lane);
 }
-// k_classic_fused whose LAST workgroup is the round's k_classic_reduce (k_sc_fused's idiom: the two block sums written through, their acknowledgement
-// awaited, a relaxed ticket; whoever draws the last one reads every block sum past its L2, publishes and puts the ticket back to zero). `counter` is the
-// ticket of ONE proof: in a merged cohort launch every blockIdx.z brings its own (and its own result and flag), gridDim.x is the same for all of them.
+KBODY k_classic_reduce(const unsigned* first, int np, const Ext* partial, Ext* result, unsigned long long* flag, unsigned long long seq) {
+  DP_LDS_FRAME(Lds_k_classic_reduce, lf);
+  classic_reduce_pairs(first, np, partial, lf.res, result, flag, seq, [](const Ext* p) { return *p; });
+}
+// k_classic_fused whose LAST workgroup is the round's k_classic_reduce (the last-workgroup epilogue: sc_store_through). `counter` is the ticket of ONE proof:
+// in a merged cohort launch every blockIdx.z brings its own (and its own result and flag), gridDim.x is the same for all of them.
 KBODY k_classic_fused_pub(const unsigned* first, const ClassicDesc* d, int np, Ext r, int has_r, Ext* partial, unsigned* counter, Ext* result, unsigned long long* flag, unsigned long long seq) {
   __shared__ Ext sm[TPB / 64];
-  __shared__ int slot, s_last;
+  __shared__ int slot;
   Ext c0 = ex_zero(), c2 = ex_zero();
   classic_fused_block(first, d, np, r, has_r, &slot, c0, c2);
   Ext t;
   t = block_reduce_ext(c0, sm); if (threadIdx.x == 0) sc_store_through(&partial[2 * (size_t)blockIdx.x], t);
   t = block_reduce_ext(c2, sm); if (threadIdx.x == 0) sc_store_through(&partial[2 * (size_t)blockIdx.x + 1], t);
-  if (threadIdx.x == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    s_last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  DP_LDS_FRAME(Lds_k_classic_reduce, lf); auto& res = lf.res;
-  const int W = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int i = wave; i < np; i += W) {
-    Ext a0 = ex_zero(), a2 = ex_zero();
-    for (unsigned w = first[i] + lane; w < first[i + 1]; w += 64) {
-      const u64* pp = (const u64*)&partial[2 * (size_t)w];
-      a0 = ex_add(a0, ex(__hip_atomic_load(pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), __hip_atomic_load(pp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)));
-      a2 = ex_add(a2, ex(__hip_atomic_load(pp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), __hip_atomic_load(pp + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)));
-    }
-    a0 = wave_reduce_ext(a0); a2 = wave_reduce_ext(a2);
-    if (lane == 0) { res[2 * i] = a0; res[2 * i + 1] = a2; }
-  }
-  __syncthreads();
-  if (wave == 0) sc_publish_vals(result, res, 1, 2 * np, flag, seq, lane);
-  if (threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // the next launch on this stream starts from zero
+  if (!sums_ticket_take(counter)) return;
+  DP_LDS_FRAME(Lds_k_classic_reduce, lf);
+  classic_reduce_pairs(first, np, partial, lf.res, result, flag, seq, [](const Ext* p) { return ld_through(p); });
+  if (threadIdx.x == 0) sums_ticket_return(counter);
 }
 struct EqDesc { Ext* out; unsigned k; unsigned pad; Ext pt[MAX_PT]; };
 // many eq tables in one launch: blockIdx.y selects the table (batch_open builds one per opened polynomial)
