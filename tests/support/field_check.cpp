@@ -1,5 +1,8 @@
-// Test support: the product's field header (deep-prove_amd/csrc/gl64.h — the very functions the gfx950 kernels inline),
-// compiled for the host and compared with plain 128-bit `%` arithmetic on edge values and a random sweep.
+// Test support: the PORTABLE branch of the product's field header (deep-prove_amd/csrc/gl64.h: what the host orchestrator, the CPU SIMT emulator and a
+// -DDP_NO_GFX950_ASM library compile), built for the host and compared with plain 128-bit `%` arithmetic on edge values and a random sweep.
+// The gfx950 kernels do NOT inline these bodies: with DP_GX_ON gl_mul / ex_mul / ex_lerp / ex_lerp_base are built from the hand-written sequences of
+// gl64_gfx950.h, which only a GPU can run — tests/support/field_probe.hip + tests/test_gpu_field_forms.py check those (and test_field_forms_host.py the
+// portable forms of gl64_lazy.h / poseidon2_fast.h that this file does not reach).
 #include "../../deep-prove_amd/csrc/gl64.h"
 #include <cstdio>
 #include <vector>

@@ -1,6 +1,7 @@
 // r04: the hand-written gfx950 Goldilocks multiplication (csrc/gl64_gfx950.h) against the compiler's — correctness on edge + random inputs
 // (host reference: 128-bit product mod p), dependent-chain latency on one wave, throughput on the full chip, and Poseidon2 compress() throughput
 // (one node per lane, 2^21 nodes) with a checksum of the digests. Build twice: default (asm) and -DDP_NO_GFX950_ASM (compiler); the checksums must agree.
+// A TIMING tool: the edge-value and rare-path checks of these sequences live in the suite (tests/support/field_probe.hip, tests/test_gpu_field_forms.py).
 #include "../../deep-prove_amd/csrc/poseidon2.h"
 #include "../../deep-prove_amd/csrc/poseidon2_fast.h"
 #include <hip/hip_runtime.h>
