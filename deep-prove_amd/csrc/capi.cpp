@@ -1,6 +1,7 @@
 // extern "C" surface of libdeepprove_hip.so (declared in include/deep_prove_hip.h).
 #include "../../include/deep_prove_hip.h"
 #include "../../include/deep_prove_hip_infer.h"
+#include "../../include/deep_prove_hip_peer.h"
 #include "zkml.h"
 #include "blob.h"
 #include "sharded.h"
@@ -21,10 +22,13 @@
 #include <map>
 #include <set>
 #include <mutex>
+#include <random>
 #include <thread>
+#include <unistd.h>
 
 DP_FIBER_SWITCH_ASM
-namespace dp { struct Cohort; Cohort* hip_cohort_new(); Cohort* hip_cohort_new_sharing(Cohort* with); void hip_cohort_free(Cohort* c); void hip_cohort_drain(Cohort* c); void hip_cohort_stats(Cohort* c, size_t* fired, size_t* packs); void hip_dev_cohort_attach(Dev* d, Cohort* c); void hip_dev_cohort_detach(Dev* d); void hip_dev_set_latency_mode(Dev* d, bool on); void hip_dev_pcs_share(Dev* worker, Dev* owner); void hip_dump_wg_times(); void hip_dev_dump_host_stats(Dev* d); size_t hip_dev_arena_peak(Dev* d); double hip_dev_probe_compress_rate(Dev* d, size_t nodes, int reps); void hip_dev_arena_peak_reset(Dev* d); void hip_mem_info(int device, size_t* free_bytes, size_t* total_bytes); void hip_dev_dump_sc_debug(Dev* d); Dev* make_hip_worker(int device, size_t arena_bytes); Dev* make_hip_dev(int device); void hip_dev_profile_enable(Dev* d, bool on); std::string hip_dev_profile_report(Dev* d); }
+namespace dp { struct Cohort; Cohort* hip_cohort_new(); Cohort* hip_cohort_new_sharing(Cohort* with); void hip_cohort_free(Cohort* c); void hip_cohort_drain(Cohort* c); void hip_cohort_stats(Cohort* c, size_t* fired, size_t* packs); void hip_dev_cohort_attach(Dev* d, Cohort* c); void hip_dev_cohort_detach(Dev* d); void hip_dev_set_latency_mode(Dev* d, bool on); void hip_dev_pcs_share(Dev* worker, Dev* owner); void hip_dump_wg_times(); void hip_dev_dump_host_stats(Dev* d); size_t hip_dev_arena_peak(Dev* d); double hip_dev_probe_compress_rate(Dev* d, size_t nodes, int reps); void hip_dev_arena_peak_reset(Dev* d); void hip_mem_info(int device, size_t* free_bytes, size_t* total_bytes); void hip_dev_dump_sc_debug(Dev* d); Dev* make_hip_worker(int device, size_t arena_bytes); Dev* make_hip_dev(int device); void hip_dev_profile_enable(Dev* d, bool on); std::string hip_dev_profile_report(Dev* d);
+void hip_dev_peer_all_gather(Dev* d, const Dev::PeerMailboxes* pm, const u64* send, size_t nwords, u64* out); }
 using namespace dp;
 
 // `mu`: PCS::commit is called from rayon workers in the reference (zkml/src/commit/context.rs:79-103 into_par_iter over
@@ -434,6 +438,130 @@ int32_t dp_sumcheck_prove_sharded_local(dp_ctx* const* ctxs, int32_t world, uint
     Writer w0; w0.iop(outs[0].proof);
     for (int g = 1; g < world; g++) { Writer w; w.iop(outs[g].proof); DP_REQUIRE(w.w == w0.w, DP_ERR_HIP, "ranks produced different proofs"); }
     sharded_out(outs[0], (size_t)ntables, proof_words, proof_nwords, finals);
+  });
+}
+}  // extern "C"
+
+// ---- the sharded sumcheck between processes: shares through peer-mapped mailboxes (include/deep_prove_hip_peer.h, csrc/peer_mailbox.h)
+namespace {
+// what a rank tells its peers about its mailbox (DP_PEER_HANDLE_BYTES bytes, plain data: it travels through files, pipes, launchers)
+struct PeerHandleBlob {
+  uint64_t magic; uint32_t version; uint32_t pid; uint64_t nonce; int32_t rank, world; uint32_t slot_words; uint32_t fine_grained;
+  hipIpcMemHandle_t ipc; uint64_t raw; uint64_t pad[2];
+};
+static_assert(sizeof(hipIpcMemHandle_t) == 64 && sizeof(PeerHandleBlob) == DP_PEER_HANDLE_BYTES, "the handle blob fills its 128 bytes");
+constexpr uint64_t PEER_MAGIC = 0x3152454550504444ULL;  // "DDPPEER1"
+constexpr uint32_t PEER_VERSION = 1;
+uint64_t peer_process_nonce() {  // tells a blob of THIS process (its mailbox is used through its address) from one of an earlier owner of the pid
+  static const uint64_t n = [] { std::random_device rd; return ((uint64_t)rd() << 32) ^ (uint64_t)rd() ^ ((uint64_t)std::chrono::steady_clock::now().time_since_epoch().count() << 1) | 1; }();
+  return n;
+}
+}  // namespace
+struct dp_peer : Exchange, Dev::ShareExchange {
+  dp_ctx* ctx = nullptr; int rank_ = 0, world_ = 1;
+  u64* box = nullptr; bool fine_grained = false;  // this rank's mailbox
+  std::vector<u64*> maps; std::vector<bool> opened;  // every rank's mailbox as mapped here; opened[i]: through hipIpcOpenMemHandle (closed in the destructor)
+  u64** table_dev = nullptr;
+  unsigned long long counter = 0;  // the group's exchange number: 1 at connect, + 1 per exchange, the same on every rank
+  bool connected = false, poisoned = false;
+  Dev::PeerMailboxes pm{nullptr, 0, 1, counter};
+  int world() const override { return world_; }
+  int rank() const override { return rank_; }
+  Dev::ShareExchange* device() override { return this; }
+  const Dev::PeerMailboxes* peer_mailboxes() override { return &pm; }
+  void all_gather_device(const u64*, size_t, u64*, void*) override { throw DpError(DP_ERR_HIP, "peer exchange: the device gathers through the mailboxes"); }
+  void usable() const {
+    DP_REQUIRE(connected, DP_ERR_ARG, "peer group: not connected (dp_peer_connect)");
+    if (poisoned) throw DpError(DP_ERR_HIP, "peer group: poisoned by an earlier error (its exchange counter may be out of step with the peers'): free it and connect a new one");
+  }
+  // the words the prover exchanges outside the rounds (do the ranks agree on device shares, stage 2's finals): the same kernel, mode GATHER
+  void all_gather(const u64* send, size_t nwords, u64* out) override {
+    usable();
+    try { hip_dev_peer_all_gather(ctx->dev, &pm, send, nwords, out); } catch (...) { poisoned = true; throw; }
+  }
+  ~dp_peer() override {
+    if (ctx) { try { ctx->dev->bind_thread(); } catch (...) {} }
+    for (size_t i = 0; i < maps.size(); i++) if (opened[i] && maps[i]) hipIpcCloseMemHandle(maps[i]);
+    if (table_dev) hipFree(table_dev);
+    if (box) hipFree(box);
+  }
+};
+extern "C" {
+int32_t dp_peer_create(dp_ctx* ctx, int32_t rank, int32_t world, dp_peer** out, uint8_t handle[DP_PEER_HANDLE_BYTES]) {
+  return guard([&] {
+    DP_REQUIRE(world >= 1 && world <= PEER_MAX_WORLD && (world & (world - 1)) == 0, DP_ERR_ARG, "peer group: world must be a power of two, 1 to 16");
+    DP_REQUIRE(rank >= 0 && rank < world, DP_ERR_ARG, "peer group: rank outside the world");
+    DP_REQUIRE(ctx && out && handle, DP_ERR_ARG, "peer group: null context / output / handle");
+    std::unique_ptr<dp_peer> p(new dp_peer());
+    p->ctx = ctx; p->rank_ = rank; p->world_ = world;
+    ctx->dev->bind_thread();
+    const size_t bytes = peer_mailbox_words(world) * 8;
+    PeerHandleBlob b; memset(&b, 0, sizeof b);
+    // fine-grained device memory (as the challenge mailbox): coherent for peers on OTHER devices too; if the runtime will not export such an allocation,
+    // an ordinary one — coherent between ranks of one device, whose accesses all bypass L1 and the XCD L2s
+    void* m = nullptr;
+    if (hipExtMallocWithFlags(&m, bytes, hipDeviceMallocFinegrained) == hipSuccess && m) {
+      if (hipIpcGetMemHandle(&b.ipc, m) == hipSuccess) p->fine_grained = true; else { (void)hipGetLastError(); hipFree(m); m = nullptr; }
+    } else { (void)hipGetLastError(); m = nullptr; }
+    if (!m) { HIPRT_CHECK(hipMalloc(&m, bytes)); p->box = (u64*)m; HIPRT_CHECK(hipIpcGetMemHandle(&b.ipc, m)); }
+    p->box = (u64*)m;
+    HIPRT_CHECK(hipMemset(m, 0, bytes));
+    HIPRT_CHECK(hipDeviceSynchronize());
+    b.magic = PEER_MAGIC; b.version = PEER_VERSION; b.pid = (uint32_t)getpid(); b.nonce = peer_process_nonce(); b.rank = rank; b.world = world;
+    b.slot_words = PEER_SLOT_WORDS; b.fine_grained = p->fine_grained ? 1 : 0; b.raw = (uint64_t)(uintptr_t)m;
+    memcpy(handle, &b, sizeof b);
+    *out = p.release();
+  });
+}
+int32_t dp_peer_connect(dp_peer* p, const uint8_t* handles) {
+  return guard([&] {
+    DP_REQUIRE(p && handles, DP_ERR_ARG, "peer group: null group / handles");
+    DP_REQUIRE(!p->connected, DP_ERR_ARG, "peer group: already connected");
+    std::vector<PeerHandleBlob> bl((size_t)p->world_);
+    for (int i = 0; i < p->world_; i++) {  // everything is checked before anything is opened
+      PeerHandleBlob& b = bl[i]; memcpy(&b, handles + (size_t)i * DP_PEER_HANDLE_BYTES, sizeof b);
+      DP_REQUIRE(b.magic == PEER_MAGIC && b.version == PEER_VERSION, DP_ERR_ARG, "peer group: handle " + std::to_string(i) + " is not a mailbox handle of this version");
+      DP_REQUIRE(b.world == p->world_, DP_ERR_ARG, "peer group: handle " + std::to_string(i) + " was made for another world size");
+      DP_REQUIRE(b.slot_words == (uint32_t)PEER_SLOT_WORDS, DP_ERR_ARG, "peer group: handle " + std::to_string(i) + " has another slot capacity");
+      DP_REQUIRE(b.rank == i, DP_ERR_ARG, "peer group: handle " + std::to_string(i) + " belongs to rank " + std::to_string(b.rank) + " (handles go in rank order)");
+      DP_REQUIRE(b.raw != 0, DP_ERR_ARG, "peer group: handle " + std::to_string(i) + " holds no mailbox");
+    }
+    { const PeerHandleBlob& b = bl[p->rank_]; DP_REQUIRE(b.pid == (uint32_t)getpid() && b.nonce == peer_process_nonce() && b.raw == (uint64_t)(uintptr_t)p->box, DP_ERR_ARG, "peer group: the handle at this rank's place is not this group's own"); }
+    p->ctx->dev->bind_thread();
+    p->maps.assign((size_t)p->world_, nullptr); p->opened.assign((size_t)p->world_, false);
+    for (int i = 0; i < p->world_; i++) {
+      const PeerHandleBlob& b = bl[i];
+      if (b.pid == (uint32_t)getpid() && b.nonce == peer_process_nonce()) { p->maps[i] = (u64*)(uintptr_t)b.raw; continue; }  // (a process cannot open its own handles)
+      void* m = nullptr;
+      HIPRT_CHECK(hipIpcOpenMemHandle(&m, b.ipc, hipIpcMemLazyEnablePeerAccess));
+      p->maps[i] = (u64*)m; p->opened[i] = true;
+    }
+    HIPRT_CHECK(hipMalloc((void**)&p->table_dev, sizeof(u64*) * (size_t)p->world_));
+    HIPRT_CHECK(hipMemcpy(p->table_dev, p->maps.data(), sizeof(u64*) * (size_t)p->world_, hipMemcpyHostToDevice));
+    p->counter = 1;
+    p->pm.table_dev = p->table_dev; p->pm.rank = p->rank_; p->pm.world = p->world_;
+    p->connected = true;
+  });
+}
+int32_t dp_peer_free(dp_peer* p) { return guard([&] { delete p; }); }
+int32_t dp_sumcheck_prove_peer(dp_ctx* ctx, dp_peer* peer, uint32_t num_vars, const dp_buf* const* tables, int32_t ntables, const int32_t* term_degree,
+                               const int32_t* term_tables, const uint64_t* term_coeffs, int32_t nterms, dp_transcript* t,
+                               uint64_t** proof_words, size_t* proof_nwords, uint64_t* finals) {
+  return guard([&] {
+    DP_REQUIRE(ctx && peer && tables && term_degree && term_tables && term_coeffs && t && proof_words && proof_nwords && ntables > 0 && nterms > 0 && num_vars > 0 && num_vars < 48, DP_ERR_ARG, "bad arguments");
+    DP_REQUIRE(peer->ctx == ctx, DP_ERR_ARG, "the peer group belongs to another context");
+    peer->usable();
+    unsigned k = 0; while ((1 << k) < peer->world()) k++;
+    DP_REQUIRE(num_vars > k, DP_ERR_SHAPE, "more ranks than table entries");
+    DevVP vp(num_vars - k);
+    read_terms(vp, tables, ntables, term_degree, term_tables, nterms, term_coeffs);
+    for (const DBuf& b : vp.tabs) DP_REQUIRE(b.n == (size_t(1) << (num_vars - k)), DP_ERR_SHAPE, "sharded sumcheck: every local table has 2^(num_vars - log2 world) entries");
+    ctx->dev->bind_thread();
+    // from here on the peers count on this rank's exchanges: whatever fails, the group's counter may be out of step with theirs
+    try {
+      SumcheckOut so = sumcheck_prove_sharded(*ctx->dev, *peer, num_vars, vp, t->t);
+      sharded_out(so, (size_t)ntables, proof_words, proof_nwords, finals);
+    } catch (...) { peer->poisoned = true; throw; }
   });
 }
 }  // extern "C"

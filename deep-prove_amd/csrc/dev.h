@@ -7,6 +7,7 @@
 // K-numbers refer to SURVEY.md §2.3 (the reference's rayon hot loops these ops replace).
 #pragma once
 #include "gl64.h"
+#include "peer_mailbox.h"
 #include "poseidon2.h"
 #include <vector>
 #include <stdexcept>
@@ -139,11 +140,17 @@ class Dev {
   // round sums in device memory, has them all-gathered there (ShareExchange: ncclAllGather over xGMI on the context's own stream),
   // adds the ranks' shares mod p in a one-workgroup kernel and publishes the TOTAL to the host — `out` then holds the sums over
   // all ranks and the round has cost one host wait. `false`: this device keeps the host exchange (the CPU test double).
+  // table_dev: the `world` mailbox base addresses as mapped in this process, in rank order, in device memory; counter: the group's exchange number (1 at
+  // connect, + 1 per exchange, identical on every rank)
+  struct PeerMailboxes { u64* const* table_dev; int rank, world; unsigned long long& counter; };
   struct ShareExchange {
     virtual ~ShareExchange() {}
     virtual int world() const = 0;
     // every rank contributes `nwords` u64 words at dsend; drecv receives world * nwords words in rank order; ordered on `stream`
     virtual void all_gather_device(const u64* dsend, size_t nwords, u64* drecv, void* stream) = 0;
+    // The peer exchange (csrc/peer_mailbox.h), for exchanges whose ranks have mapped each other's mailboxes: non-null — the device posts this rank's words
+    // straight into every peer's mailbox, polls its own and adds the shares in ONE kernel (k_peer_exchange_publish), and all_gather_device is never called.
+    virtual const PeerMailboxes* peer_mailboxes() { return nullptr; }
   };
   virtual bool sc_set_share_exchange(ShareExchange* x) { (void)x; return false; }
   // All remaining rounds of a sumcheck WITH its Fiat-Shamir transcript on the device, for devices that can keep the sponge

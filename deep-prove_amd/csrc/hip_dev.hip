@@ -469,15 +469,53 @@ class HipDev : public Dev {
     if (x && (queued_() || !zerocopy_)) return false;
     if (x) {
       if (!dshare_) HIP_CHECK(hipMalloc((void**)&dshare_, (RES_WORDS + 8) * 8));
-      const size_t need = RES_WORDS * (size_t)x->world();
+      const size_t need = x->peer_mailboxes() ? 0 : RES_WORDS * (size_t)x->world();  // (the peer exchange gathers in its kernel's LDS)
       if (dgather_words_ < need) { if (dgather_) { HIP_CHECK(hipStreamSynchronize(s_)); HIP_CHECK(hipFree(dgather_)); } HIP_CHECK(hipMalloc((void**)&dgather_, need * 8)); dgather_words_ = need; }
     }
     share_x_ = x;
     return true;
   }
+  // One exchange through the peers' mailboxes (k_peer_exchange_publish): `words` — this rank's `nwords` words, readable by the device — are posted to every
+  // rank, every rank's are gathered, and hres_ receives their mod-p sum (PEER_MODE_SUM, nwords words) or all of them in rank order (PEER_MODE_GATHER). One launch,
+  // one wait. The group's counter moves on BEFORE anything can fail: an exchange that fails leaves the group out of step (capi.cpp poisons it).
+  void peer_exchange_(const PeerMailboxes& pm, int mode, const u64* words, size_t nwords) {
+    DP_REQUIRE(zerocopy_ && !queued_(), DP_ERR_ARG, "the peer exchange needs zero-copy results and a context outside a cohort");
+    DP_REQUIRE(pm.table_dev && pm.world >= 1 && pm.world <= PEER_MAX_WORLD && pm.rank >= 0 && pm.rank < pm.world, DP_ERR_ARG, "peer exchange: bad group");
+    DP_REQUIRE(nwords >= 1 && nwords <= (size_t)PEER_SLOT_WORDS && (mode != PEER_MODE_SUM || nwords % 2 == 0) && nwords * (size_t)pm.world <= RES_WORDS, DP_ERR_SHAPE, "peer exchange: message too large");
+    const unsigned long long xnum = pm.counter++;
+    const unsigned long long seq = ++seq_;
+    const int threads = 64 * std::min(std::max(pm.world, 4), 16);  // a wave per sender (at least four: the long-message path strides over all of them)
+    nb_ = 8.0 * (double)nwords * pm.world * 2;
+    DPL(k_peer_exchange_publish, dim3(1), dim3(threads), words, (int)nwords, pm.table_dev, pm.rank, pm.world, xnum, mode, (Ext*)hres_dev_, hflag_dev_, seq);
+    try { wait_flag(seq, mode == PEER_MODE_SUM ? nwords : nwords * (size_t)pm.world); }
+    catch (const DpError&) {
+      if (*(volatile unsigned long long*)hflag_ == ~0ull) throw DpError(DP_ERR_HIP, "sharded sumcheck: a peer did not post its shares in time");
+      throw;
+    }
+  }
+ public:
+  // Exchange::all_gather over the peers' mailboxes: `send` (host) travels in the descriptor ring, `out` receives world * nwords words in rank order
+  void peer_all_gather(const PeerMailboxes& pm, const u64* send, size_t nwords, u64* out) {
+    DP_REQUIRE(send && out && nwords >= 1 && nwords <= (size_t)PEER_SLOT_WORDS, DP_ERR_SHAPE, "peer exchange: message too large");
+    const u64* dview = nullptr;
+    u64* h = desc_alloc<u64>(nwords, &dview);
+    memcpy(h, send, nwords * 8);
+    std::atomic_thread_fence(std::memory_order_release);
+    peer_exchange_(pm, PEER_MODE_GATHER, dview, nwords);
+    for (size_t i = 0; i < nwords * (size_t)pm.world; i++) out[i] = hres_[i];
+  }
+ private:
   // this rank's `nwords` raw words sit at dshare_: gather the ranks' words, add them mod p, bring the total to hres_ (one wait)
+  // (a round of more than MAX_TERMS terms runs as several launches, sc_round: each leaves its words behind the previous one's — share_words_() — and only the
+  // last one exchanges, all of them at once)
+  size_t share_off_ = 0; bool share_defer_ = false;
+  u64* share_words_() const { return dshare_ + share_off_; }
   void share_exchange_(size_t nwords) {
+    nwords += share_off_;
     DP_REQUIRE(nwords % 2 == 0 && nwords <= RES_WORDS && nwords / 2 <= 1024, DP_ERR_SHAPE, "sharded sumcheck: round message too large");
+    if (share_defer_) { share_off_ = nwords; return; }
+    share_off_ = 0;
+    if (const PeerMailboxes* pm = share_x_->peer_mailboxes()) { peer_exchange_(*pm, PEER_MODE_SUM, dshare_, nwords); return; }
     share_x_->all_gather_device(dshare_, nwords, dgather_, (void*)s_);
     unsigned long long seq = ++seq_;
     nb_ = 8.0 * (double)nwords * share_x_->world(); DPL(k_shares_sum_publish, dim3(1), dim3(256), (const u64*)dgather_, share_x_->world(), (int)(nwords / 2), (Ext*)hres_dev_, hflag_dev_, seq);
@@ -488,7 +526,7 @@ class HipDev : public Dev {
     DP_REQUIRE(nout >= 1 && nout <= 1024 && (size_t)nout * 2 <= RES_WORDS, DP_ERR_SHAPE, "reduce_publish: too many outputs");
     if (share_x_) {  // the reduction lands in device memory (the tag word too: nobody reads it), the exchange brings the ranks' total to hres_
       int threads = nout >= 8 ? 1024 : nout >= 4 ? 256 : 64 * nout;
-      DPL(k_reduce_publish, dim3(1), dim3(threads), partial, nblocks, inner, nout, (Ext*)dshare_, (unsigned long long*)(dshare_ + RES_WORDS), 0ull);
+      DPL(k_reduce_publish, dim3(1), dim3(threads), partial, nblocks, inner, nout, (Ext*)share_words_(), (unsigned long long*)(dshare_ + RES_WORDS), 0ull);
       share_exchange_((size_t)nout * 2);
       return;
     }
@@ -1424,6 +1462,27 @@ class HipDev : public Dev {
     return true;
   }
   void sc_round(DBuf* tabs, int nt, const Ext* r, const ScTerm* terms, int nterms, Ext* out) override {
+    if (nterms > MAX_TERMS) {
+      // More terms than one launch takes (a sharded round of a hundred small terms): the round runs as several launches over equal parts of the terms — no part
+      // is a single product, which has forms of its own — the first of which folds. No session spans launches that carry different terms. Sharded (share_x_),
+      // the parts leave their shares side by side in dshare_ and the LAST one exchanges the whole message: one exchange per round, whatever the number of terms.
+      DP_REQUIRE(!sess_.active && !grid2_.stage && !queued_(), DP_ERR_ARG, "sumcheck out of sync (a round of more than MAX_TERMS terms inside a session or a cohort)");
+      size_t total = 0, sofar = 0;
+      for (int i = 0; i < nterms; i++) { DP_REQUIRE(terms[i].k >= 1 && terms[i].k <= SC_MAXK, DP_ERR_SHAPE, "sumcheck: term degree must be 1..5"); total += terms[i].k + 1; }
+      DP_REQUIRE(total <= 1024, DP_ERR_SHAPE, "sumcheck: round message too large");
+      const int nparts = (nterms + MAX_TERMS - 1) / MAX_TERMS, per = (nterms + nparts - 1) / nparts;
+      struct Reset { HipDev* d; bool persist; ~Reset() { d->persist_ = persist; d->share_defer_ = false; d->share_off_ = 0; } } reset{this, persist_};
+      persist_ = false;
+      for (int o = 0; o < nterms; o += per) {
+        const int c = std::min(per, nterms - o);
+        share_defer_ = share_x_ && o + c < nterms;
+        sc_round(tabs, nt, o == 0 ? r : nullptr, terms + o, c, share_x_ ? out : out + sofar);
+        for (int i = o; i < o + c; i++) sofar += terms[i].k + 1;
+        DP_REQUIRE(!share_defer_ || share_off_ == 2 * sofar, DP_ERR_SHAPE, "sharded sumcheck: a launch left more words than its terms have values");
+      }
+      if (share_x_) for (size_t v = 0; v < total; v++) out[v] = ex(hres_[2 * v], hres_[2 * v + 1]);
+      return;
+    }
     DP_REQUIRE(nt <= MAX_TABS && nterms <= MAX_TERMS && nt > 0 && nterms > 0, DP_ERR_SHAPE, "sumcheck: too many tables/terms for one launch");
     size_t n_in = tabs[0].n;
     for (int i = 0; i < nt; i++) DP_REQUIRE(tabs[i].n == n_in, DP_ERR_SHAPE, "sumcheck: tables must have equal length");
@@ -1642,7 +1701,7 @@ class HipDev : public Dev {
       unsigned long long seq = ++seq_;
       size_t work = (size_t)nterms * (n_after / 2) + (r ? (size_t)nt * n_after / 4 : 0);
       int threads = persist_threads(work);
-      if (share_x_) { nb_ = bytes; DPL_ONE_HI(k_sc_small, hi, dim3(1), threads, 0, a, (Ext*)dshare_, (unsigned long long*)(dshare_ + RES_WORDS), seq); share_exchange_(2 * nraw); read_terms(); return; }
+      if (share_x_) { nb_ = bytes; DPL_ONE_HI(k_sc_small, hi, dim3(1), threads, 0, a, (Ext*)share_words_(), (unsigned long long*)(dshare_ + RES_WORDS), seq); share_exchange_(2 * nraw); read_terms(); return; }
       nb_ = bytes; DPL_ONE_HI(k_sc_small, hi, dim3(1), threads, 0, a, (Ext*)hres_dev_, hflag_dev_, seq);
       wait_flag(seq, 2 * nraw);
       read_terms();
@@ -2358,6 +2417,7 @@ void hip_dump_wg_times() {
 }
 void hip_dev_pcs_share(Dev* worker, Dev* owner) { static_cast<HipDev*>(worker)->pcs_share(*static_cast<HipDev*>(owner)); }
 void hip_dev_set_latency_mode(Dev* d, bool on) { static_cast<HipDev*>(d)->set_latency_mode(on); }
+void hip_dev_peer_all_gather(Dev* d, const Dev::PeerMailboxes* pm, const u64* send, size_t nwords, u64* out) { static_cast<HipDev*>(d)->peer_all_gather(*pm, send, nwords, out); }
 void hip_dev_profile_enable(Dev* d, bool on) { static_cast<HipDev*>(d)->profile_enable(on); }
 std::string hip_dev_profile_report(Dev* d) { return static_cast<HipDev*>(d)->profile_report(); }
 

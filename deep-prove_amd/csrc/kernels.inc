@@ -2893,6 +2893,97 @@ KBODY k_shares_sum_publish(const u64* gathered, int world, int next, Ext* result
   __syncthreads();
   if (threadIdx.x < 64) sc_publish_vals(result, res, 1, next, flag, seq, threadIdx.x);
 }
+// sharded sumcheck, peer exchange (csrc/peer_mailbox.h holds the protocol and the argument why two parities suffice): the all-gather AND what follows it in
+// one one-workgroup kernel, with no collective library and no host hop between the ranks. `mine`: this rank's `nwords` words; `boxes`: the `world` mailbox
+// base addresses as mapped in THIS process (device memory, rank order); `xnum`: the group's exchange number.
+//  (a) post: the words and their tag go into slot (xnum & 1, rank) of EVERY rank's mailbox, this rank's own included — relaxed system-scope stores, destinations
+//      strided over the waves;
+//  (b) gather: slot (xnum & 1, sender) of this rank's OWN mailbox is polled for every sender with relaxed system-scope loads (every load of mailbox bytes is
+//      such a load: it bypasses L1, and a stale or torn read fails the tag and is read again) until the tag verifies; a sleep between polls, the wait bounded in
+//      TIME by c_poll_timeout_ticks as wc_poll_pause bounds its own; on timeout the failure marker ~0 goes to the host flag and the kernel ends;
+//  (c) publish: PEER_MODE_SUM — the shares added mod p (nwords even), as k_shares_sum_publish; PEER_MODE_GATHER — the world x nwords words in rank order.
+// Messages of up to PEER_FAST_WORDS words (32 extension values: every round of the usual virtual polynomials) take the fast path: one wave per sender polls its
+// slot — one word per lane, the checksum a wave reduction — all senders at once, and leaves the validated words in LDS. Longer ones, up to PEER_SLOT_WORDS, are
+// read sender by sender by the whole workgroup.
+constexpr int PEER_FAST_WORDS = 64;
+struct PeerSt { __device__ __forceinline__ void operator()(u64* p, u64 v) const { pub_store(p, v); } };
+struct PeerLd { __device__ __forceinline__ u64 operator()(const u64* p) const { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); } };
+__device__ __forceinline__ bool peer_poll_pause(unsigned long long t0, unsigned spin) {
+  if ((spin & 63) == 63 && dp_realtime() - t0 > c_poll_timeout_ticks) return true;
+  for (int q = 0; q < c_poll_sleep; q++) __builtin_amdgcn_s_sleep(4);
+  return false;
+}
+struct alignas(16) Lds_k_peer_exchange_publish { u64 buf[PEER_SLOT_WORDS]; u64 acc[PEER_SLOT_WORDS]; unsigned long long part[16]; int status; int fail; };
+KBODY k_peer_exchange_publish(const u64* mine, int nwords, u64* const* boxes, int rank, int world, unsigned long long xnum, int mode, Ext* result, unsigned long long* flag, unsigned long long seq) {
+  DP_LDS_FRAME(Lds_k_peer_exchange_publish, lf);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+  if (tid == 0) lf.fail = 0;
+  for (int d = wave; d < world; d += nwaves) {
+    u64* slot = boxes[d] + peer_slot(xnum, rank, world);
+    const u64 cs = pub_wave_sum(peer_post_words(PeerSt(), slot, mine, (size_t)nwords, (size_t)lane, (size_t)64));
+    if (lane == 0) pub_store(slot + PEER_SLOT_WORDS, peer_tag(xnum, cs, (size_t)nwords));
+  }
+  __syncthreads();
+  const u64* box = boxes[rank];
+  u64* rw = (u64*)result;
+  const unsigned long long t0 = dp_realtime();
+  if (nwords <= PEER_FAST_WORDS) {
+    for (int s = wave; s < world; s += nwaves) {
+      const u64* slot = box + peer_slot(xnum, s, world);
+      bool gone = false;
+      for (unsigned spin = 0;; spin++) {
+        const u64 v = lane < nwords ? PeerLd()(slot + lane) : 0;
+        const u64 tag = PeerLd()(slot + PEER_SLOT_WORDS);
+        const u64 cs = pub_wave_sum((u64)(lane + 1) * v);  // (lane 0 holds the sum, and decides for the wave)
+        if (__shfl((int)(tag == peer_tag(xnum, cs, (size_t)nwords)), 0, 64)) { lf.buf[s * PEER_FAST_WORDS + lane] = v; break; }
+        if (__shfl((int)peer_poll_pause(t0, spin), 0, 64)) { gone = true; break; }
+      }
+      if (gone) { if (lane == 0) lf.fail = 1; break; }
+    }
+    __syncthreads();
+    if (lf.fail) { if (tid == 0) pub_store((u64*)flag, ~0ull); return; }
+    if (mode == PEER_MODE_SUM) {
+      if (tid < nwords) { u64 a = 0; for (int s = 0; s < world; s++) a = gl_add(a, lf.buf[s * PEER_FAST_WORDS + tid]); lf.acc[tid] = a; }
+      __syncthreads();
+      if (wave == 0) sc_publish_vals(result, (const Ext*)lf.acc, 1, nwords / 2, flag, seq, lane);
+    } else if (wave == 0) {
+      unsigned long long cs = 0;
+      for (int idx = lane; idx < world * nwords; idx += 64) {
+        const int s = idx / nwords, i = idx - s * nwords;
+        const u64 v = lf.buf[s * PEER_FAST_WORDS + i];
+        pub_store(rw + idx, v); cs += (unsigned long long)(idx + 1) * v;
+      }
+      cs = pub_wave_sum(cs);
+      if (lane == 0) pub_store((u64*)flag, pub_mix(seq) + cs);
+    }
+    return;
+  }
+  unsigned long long gcs = 0;  // PEER_MODE_GATHER: this thread's share of the checksum of the message to the host
+  for (int i = tid; i < nwords; i += blockDim.x) lf.acc[i] = 0;
+  for (int s = 0; s < world; s++) {
+    const u64* slot = box + peer_slot(xnum, s, world);
+    for (unsigned spin = 0;; spin++) {
+      const u64 cs = pub_wave_sum(peer_read_words(PeerLd(), slot, lf.buf, (size_t)nwords, (size_t)tid, (size_t)blockDim.x));
+      if (lane == 0) lf.part[wave] = cs;
+      __syncthreads();
+      if (tid == 0) {
+        u64 t = 0; for (int w = 0; w < nwaves; w++) t += lf.part[w];
+        lf.status = PeerLd()(slot + PEER_SLOT_WORDS) == peer_tag(xnum, t, (size_t)nwords) ? 1 : peer_poll_pause(t0, spin) ? 2 : 0;
+      }
+      __syncthreads();
+      if (lf.status) break;  // (the same word for every thread: thread 0 writes it again only behind the next barrier)
+    }
+    if (lf.status == 2) { if (tid == 0) pub_store((u64*)flag, ~0ull); return; }
+    if (mode == PEER_MODE_SUM) peer_sum_into(lf.acc, lf.buf, (size_t)nwords, (size_t)tid, (size_t)blockDim.x);
+    else for (int i = tid; i < nwords; i += blockDim.x) { const size_t idx = (size_t)s * nwords + i; const u64 v = lf.buf[i]; pub_store(rw + idx, v); gcs += (unsigned long long)(idx + 1) * v; }
+    __syncthreads();  // lf.buf and lf.status are free for the next sender
+  }
+  if (mode == PEER_MODE_SUM) { if (wave == 0) sc_publish_vals(result, (const Ext*)lf.acc, 1, nwords / 2, flag, seq, lane); return; }
+  gcs = pub_wave_sum(gcs);
+  if (lane == 0) lf.part[wave] = gcs;
+  __syncthreads();
+  if (tid == 0) { unsigned long long t = 0; for (int w = 0; w < nwaves; w++) t += lf.part[w]; pub_store((u64*)flag, pub_mix(seq) + t); }
+}
 // lane 0 of wave 0: poll the host mailbox [seq, c0, c1, tag] for `seq`, leave {ok, c0, c1} in chal[]. The seq word is polled
 // with relaxed loads; once it matches, an acquire fence orders the payload loads after it, and the tag word — mix(seq) + c0 +
 // 2*c1, written by the host with the payload (post_challenge) — is checked against what was read: a stale or torn payload is

@@ -235,6 +235,77 @@ def prove_sharded_in_library(dev, group, nv, local_tables, terms, transcript):
     return _take(pw, pn.value), finals
 
 
+# ---------------------------------------------------------------- ranks as PROCESSES: shares through peer-mapped mailboxes (include/deep_prove_hip_peer.h)
+PEER_HANDLE_BYTES = 128  # DP_PEER_HANDLE_BYTES
+# name -> (restype, argtypes): every symbol declared in include/deep_prove_hip_peer.h (a binding table of its own, as infer.INFER_SIGNATURES:
+# `_lib.SIGNATURES` lists exactly the symbols of include/deep_prove_hip.h)
+PEER_SIGNATURES = {
+    "dp_peer_create": (C.c_int32, [vp, C.c_int32, C.c_int32, C.POINTER(vp), C.POINTER(C.c_uint8)]),
+    "dp_peer_connect": (C.c_int32, [vp, C.POINTER(C.c_uint8)]),
+    "dp_peer_free": (C.c_int32, [vp]),
+    "dp_sumcheck_prove_peer": (C.c_int32, [vp, vp, C.c_uint32, C.POINTER(vp), C.c_int32, _lib.i32p, _lib.i32p, _lib.u64p, C.c_int32, vp, C.POINTER(_lib.u64p), C.POINTER(C.c_size_t), _lib.u64p]),
+}
+_peer_bound = None
+
+
+def _peer_lib():
+    global _peer_bound
+    if _peer_bound is None:
+        lib = _lib.load()
+        for name, (res, args) in PEER_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _peer_bound = lib
+    return _peer_bound
+
+
+class PeerGroup:
+    """dp_peer: this rank's mailbox and, once connected, the mappings of every peer's. `handle` (128 bytes) describes the mailbox: the ranks exchange their
+    handles by any means (files, pipes, a launcher) and every rank calls connect() with all of them in rank order, its own included. The ranks may be processes
+    (one per device, or several on one device) or contexts of one process. Nobody calls close() while a peer may still post to it: synchronise first."""
+
+    def __init__(self, dev, rank, world):
+        lib = _peer_lib()
+        self.rank, self.world = rank, world
+        self.h = vp()
+        buf = (C.c_uint8 * PEER_HANDLE_BYTES)()
+        check(lib.dp_peer_create(dev.h, rank, world, C.byref(self.h), buf))
+        self.handle = bytes(buf)
+
+    @property
+    def fine_grained(self):
+        """whether the runtime exported a fine-grained allocation (else the mailbox is ordinary device memory: coherent between ranks of ONE device only)"""
+        return int.from_bytes(self.handle[36:40], "little") == 1
+
+    def connect(self, handles):
+        blob = b"".join(bytes(h) for h in handles)
+        if len(handles) != self.world or len(blob) != self.world * PEER_HANDLE_BYTES:
+            raise _lib.DeepProveError(-1, f"PeerGroup.connect: {self.world} handles of {PEER_HANDLE_BYTES} bytes are needed, in rank order")  # DP_ERR_ARG
+        arr = (C.c_uint8 * len(blob)).from_buffer_copy(blob)
+        check(_peer_lib().dp_peer_connect(self.h, arr))
+
+    def close(self):
+        if self.h:
+            _peer_lib().dp_peer_free(self.h)
+            self.h = vp()
+
+
+def prove_sharded_peer(dev, group, nv, local_tables, terms, transcript):
+    """dp_sumcheck_prove_peer: prove_sharded_in_library with the ranks' shares exchanged through the peers' mailboxes (one kernel per round posts, gathers and
+    adds them). `group`: a connected PeerGroup; every rank makes the same call. Returns (proof_words, finals) as api.prove_parallel, identical on every rank."""
+    from .api import _take
+    lib = _peer_lib()
+    nt = len(local_tables)
+    tabs = (vp * nt)(*[t.h for t in local_tables])
+    deg, tt, co = _pack_terms(terms)
+    pw, pn = _lib.u64p(), C.c_size_t()
+    finals = np.zeros(2 * nt, dtype=np.uint64)
+    check(lib.dp_sumcheck_prove_peer(dev.h, group.h, nv, tabs, nt, deg.ctypes.data_as(_lib.i32p), tt.ctypes.data_as(_lib.i32p),
+                                     co.ctypes.data_as(_lib.u64p), len(terms), transcript.h, C.byref(pw), C.byref(pn), finals.ctypes.data_as(_lib.u64p)))
+    return _take(pw, pn.value), finals
+
+
 def prove_sharded_local(devs, nv, tables_per_rank, terms, transcripts):
     """dp_sumcheck_prove_sharded_local: `len(devs)` contexts of ONE process (threads + an in-memory exchange)"""
     from .api import _take

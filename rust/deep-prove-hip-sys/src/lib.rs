@@ -134,3 +134,7 @@ unsafe impl Sync for Words {}
 /// `include/deep_prove_hip_infer.h`: batched quantised inference on the device (`dp_model_infer`), declared in a module of its own.
 pub mod infer;
 pub use infer::{dp_model_infer, dp_model_infer_checked, dp_model_infer_ex, DP_INFER_ALL_KINDS};
+
+/// `include/deep_prove_hip_peer.h`: the sharded sumcheck between processes, shares through peer-mapped mailboxes (`dp_peer_*`), in a module of its own.
+pub mod peer;
+pub use peer::{dp_peer, dp_peer_connect, dp_peer_create, dp_peer_free, dp_sumcheck_prove_peer, DP_PEER_HANDLE_BYTES};
