@@ -27,7 +27,7 @@
 #include <unistd.h>
 
 DP_FIBER_SWITCH_ASM
-namespace dp { struct Cohort; Cohort* hip_cohort_new(); Cohort* hip_cohort_new_sharing(Cohort* with); void hip_cohort_free(Cohort* c); void hip_cohort_drain(Cohort* c); void hip_cohort_stats(Cohort* c, size_t* fired, size_t* packs); void hip_dev_cohort_attach(Dev* d, Cohort* c); void hip_dev_cohort_detach(Dev* d); void hip_dev_set_latency_mode(Dev* d, bool on); void hip_dev_pcs_share(Dev* worker, Dev* owner); void hip_dump_wg_times(); void hip_dev_dump_host_stats(Dev* d); size_t hip_dev_arena_peak(Dev* d); double hip_dev_probe_compress_rate(Dev* d, size_t nodes, int reps); void hip_dev_arena_peak_reset(Dev* d); void hip_mem_info(int device, size_t* free_bytes, size_t* total_bytes); void hip_dev_dump_sc_debug(Dev* d); Dev* make_hip_worker(int device, size_t arena_bytes); Dev* make_hip_dev(int device); void hip_dev_profile_enable(Dev* d, bool on); std::string hip_dev_profile_report(Dev* d);
+namespace dp { struct Cohort; Cohort* hip_cohort_new(); void hip_cohort_lead(Cohort* c, size_t n); void hip_cohort_follow(Cohort* c, Cohort* leader); void hip_cohort_free(Cohort* c); void hip_cohort_drain(Cohort* c); void hip_cohort_stats(Cohort* c, size_t* fired, size_t* packs); void hip_dev_cohort_attach(Dev* d, Cohort* c); void hip_dev_cohort_detach(Dev* d); void hip_dev_set_latency_mode(Dev* d, bool on); void hip_dev_pcs_share(Dev* worker, Dev* owner); void hip_dump_wg_times(); void hip_dev_dump_host_stats(Dev* d); size_t hip_dev_arena_peak(Dev* d); double hip_dev_probe_compress_rate(Dev* d, size_t nodes, int reps); void hip_dev_arena_peak_reset(Dev* d); void hip_mem_info(int device, size_t* free_bytes, size_t* total_bytes); void hip_dev_dump_sc_debug(Dev* d); Dev* make_hip_worker(int device, size_t arena_bytes); Dev* make_hip_dev(int device); void hip_dev_profile_enable(Dev* d, bool on); std::string hip_dev_profile_report(Dev* d);
 void hip_dev_peer_all_gather(Dev* d, const Dev::PeerMailboxes* pm, const u64* send, size_t nwords, u64* out); }
 using namespace dp;
 
@@ -58,14 +58,15 @@ struct dp_model {
   // dp_model_infer: the flattened model and its constants on the device, made at the first call (dp_model_setup allocates nothing for them)
   // ([flags]: a program per flag word of dp_model_infer_ex, each with its constants)
   std::unique_ptr<InferProgram> infer_prog[2]; InferDeviceState* infer_state[2] = {nullptr, nullptr};
-  ~dp_model() { for (size_t i = cohorts.size(); i-- > 0;) hip_cohort_free(cohorts[i]); for (InferDeviceState* st : infer_state) if (st) hip_infer_state_free(st); }  // (last first: a cohort that shares a stream goes before the one that owns it)
+  ~dp_model() { for (size_t i = cohorts.size(); i-- > 0;) hip_cohort_free(cohorts[i]); for (InferDeviceState* st : infer_state) if (st) hip_infer_state_free(st); }  // (a launch group lives as long as any cohort that launches through it)
 };
 
-// Every cohort stream needs a hardware queue of its own (24 are served without time slicing; the HIP runtime multiplexes streams
+// Every cohort stream wants a hardware queue of its own (24 are served without time slicing; the HIP runtime multiplexes streams
 // onto GPU_MAX_HW_QUEUES = 4 by default and reads the variable when it initialises, i.e. at the first HIP call of the process).
-// The library asks for 24 when it is loaded — a host that has not touched HIP yet needs to know nothing; one that has already
-// initialised HIP keeps its setting (dp_model_prove_batch then simply shares queues: slower, not wrong, since no kernel of the
-// throughput path waits for the host).
+// The library asks for 24 when it is loaded — a host that has not touched HIP yet needs to know nothing; one that has preset the
+// variable keeps its setting, and dp_model_prove_batch then READS it: with fewer queues than cohorts, the cohorts that would share a
+// queue launch through one launch group (csrc/cohort.h) — one stream per queue, launch number i of all their members one kernel —
+// instead of queueing their launches behind each other. The variable is never set or changed after this point.
 __attribute__((constructor)) static void dp_default_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "24", 0); }
 // the host transcript's Poseidon2: the AVX-512 permutation of p2_avx512.cpp when the CPU has it (DP_NO_AVX512=1: the scalar code)
 __attribute__((constructor)) static void dp_install_fast_poseidon2() {
@@ -858,7 +859,7 @@ void async_thread(dp_async* a) {
     std::unique_ptr<AsyncGroup> g(new AsyncGroup());
     g->merged = group.size() > 1; g->devs = devs; g->live = group.size();
     try {
-      if (g->merged) { if (idle_cohorts.empty()) idle_cohorts.push_back(hip_cohort_new()); g->cohort = idle_cohorts.back(); idle_cohorts.pop_back(); }
+      if (g->merged) { if (idle_cohorts.empty()) { dp::Cohort* c = hip_cohort_new(); try { hip_cohort_lead(c, 1); } catch (...) { hip_cohort_free(c); throw; } idle_cohorts.push_back(c); } g->cohort = idle_cohorts.back(); idle_cohorts.pop_back(); }
       for (Dev* d : devs) { hip_dev_set_latency_mode(d, false); if (g->merged) hip_dev_cohort_attach(d, g->cohort); }
     } catch (const std::exception& e) {
       for (dp_ticket* t : group) { t->err = e.what(); t->state.store(DP_ERR_HIP, std::memory_order_release); }
@@ -1321,19 +1322,31 @@ int32_t dp_model_prove_batch(dp_model* m, const int64_t* inputs, size_t nproofs,
     // several proofs in flight: throughput mode on every context (see hip_dev_set_latency_mode)
     hip_dev_set_latency_mode(m->ctx->dev, nw == 1);
     for (auto& w : m->workers) hip_dev_set_latency_mode(w.get(), nw == 1);
-    // Cohorts (hip_dev.hip, struct Cohort): the proofs in flight are grouped into cohorts of DP_COHORT members (default: in flight / 22, rounded up)
-    // that prove in lock step — launch number i of all members of a cohort is ONE kernel launch — on one stream and one
-    // host thread per cohort. DP_COHORT=0: every proof on its own stream (the round-1 scheme).
+    // Cohorts (hip_dev.hip struct Cohort, cohort.h): the proofs in flight are grouped into cohorts of DP_COHORT members (default: in flight / 22, rounded up)
+    // that prove in lock step — launch number i of all members of a cohort is ONE kernel launch — with one host thread per cohort.
+    // DP_COHORT=0: every proof on its own stream (the round-1 scheme).
     const char* ce = getenv("DP_COHORT");
     // Default: as many cohorts as hardware queues serve without time slicing (22 of the 24), each as small as that allows — a merged
     // launch ends with its slowest member, so small cohorts stall less (batch of 8: 121 ms with cohorts of 1, 165 ms with one cohort
     // of 8; batch of 64: 262 ms with cohorts of 3, 302 ms with 12; 256 in flight: cohorts of 12; profiles/r02_batch_cohort_sweep.txt)
-    // DP_STREAM_SHARE = k (default 1): k cohorts take turns on one stream (hardware queue) — cohorts of in flight / (22 k) members, and while one cohort's members
-    // digest a result on the host its queue-mate's launch runs
-    const size_t share = (size_t)std::max(1, getenv("DP_STREAM_SHARE") ? atoi(getenv("DP_STREAM_SHARE")) : 1);
-    size_t csize = ce ? (size_t)std::max(0, atoi(ce)) : std::max<size_t>(1, (nw + 22 * share - 1) / (22 * share));
+    size_t csize = ce ? (size_t)std::max(0, atoi(ce)) : std::max<size_t>(1, (nw + 22 - 1) / 22);
     size_t nco = (csize >= 1 && nw > 1) ? (nw + csize - 1) / csize : 0;
-    while (m->cohorts.size() < nco) { const size_t c = m->cohorts.size(); m->cohorts.push_back(c % share ? hip_cohort_new_sharing(m->cohorts[c - c % share]) : hip_cohort_new()); }
+    while (m->cohorts.size() < nco) m->cohorts.push_back(hip_cohort_new());
+    // Launch groups (cohort.h): the cohorts are dealt round robin to DP_LAUNCH_GROUPS groups — default: the hardware queues of the process (GPU_MAX_HW_QUEUES, which
+    // the constructor above guarantees is present) when there are fewer of them than cohorts, otherwise one group per cohort, i.e. every cohort launches on
+    // its own as it always has. The cohorts of a group share one stream, one argument ring (the sum of theirs) and every launch: streams that share a hardware
+    // queue run their kernels one after the other, and a one-workgroup tail lasts as long as a member's dependent chain however many members it has — five or
+    // six cohorts on one queue pay it five or six times in a row, a group once. Host work stays where it was: one thread per cohort (cohorts of 176 on four
+    // threads are host-bound, NOTES_NEXT_ROUND.md). DP_STREAM_SHARE (cohorts taking turns on one stream, measured -3 % / -11 %,
+    // profiles/r05_stream_share_ab.txt) went with this: a group is the same sharing with the launches merged.
+    size_t ngroups = nco;
+    if (const char* ge = getenv("DP_LAUNCH_GROUPS")) ngroups = (size_t)std::max(1, atoi(ge));
+    else if (const char* qe = getenv("GPU_MAX_HW_QUEUES")) { const int nq = atoi(qe); if (nq >= 1 && (size_t)nq < nco) ngroups = (size_t)nq; }
+    ngroups = std::min(ngroups, nco);
+    for (size_t c = 0; c < nco; c++) {
+      if (c < ngroups) hip_cohort_lead(m->cohorts[c], (nco - c + ngroups - 1) / ngroups);  // cohorts c, c + ngroups, c + 2 ngroups, ...
+      else hip_cohort_follow(m->cohorts[c], m->cohorts[c % ngroups]);
+    }
     auto dev_of = [&](size_t wi) -> Dev& { return wi == 0 ? *m->ctx->dev : *m->workers[wi - 1]; };
     std::atomic<size_t> next(0);
     const bool timing = getenv("DP_TIMING") && atoi(getenv("DP_TIMING"));
@@ -1431,7 +1444,7 @@ int32_t dp_model_prove_batch(dp_model* m, const int64_t* inputs, size_t nproofs,
       if (nco) { try { hip_dev_cohort_detach(&dev); } catch (const std::exception& e) { std::lock_guard<std::mutex> g(err_mu); if (!err_code) { err_code = DP_ERR_HIP; err = e.what(); } next = nproofs; } }
     };
     // `nw` proofs in flight on `nth` host threads: every worker is a fiber; a thread switches to its next fiber whenever the
-    // current one waits for the device (fiber.h). All members of a cohort live on one thread (the cohort has no locks);
+    // current one waits for the device (fiber.h). All members of a cohort live on one thread (what several cohorts share is their launch group's, behind its lock);
     // cohorts (or, without cohorts, workers) are dealt round robin to the threads. The thread count follows the CPUs the
     // process may really use (cgroup quota), leaving two for the HIP runtime's own threads.
     const char* te = getenv("DP_HOST_THREADS");
@@ -1470,10 +1483,11 @@ int32_t dp_model_prove_batch(dp_model* m, const int64_t* inputs, size_t nproofs,
     { std::lock_guard<std::mutex> g(ser_mu); ser_stop = true; }
     ser_cv.notify_all();
     for (auto& t : sth) t.join();  // (they leave when the queue is empty: every proof is serialised and copied out)
-    for (size_t c = 0; c < nco; c++) { try { hip_cohort_drain(m->cohorts[c]); } catch (const std::exception& e) { if (!err_code) { err_code = DP_ERR_HIP; err = e.what(); } } }
+    for (size_t c = 0; c < ngroups; c++) { try { hip_cohort_drain(m->cohorts[c]); } catch (const std::exception& e) { if (!err_code) { err_code = DP_ERR_HIP; err = e.what(); } } }
     if (nco && getenv("DP_TIMING") && atoi(getenv("DP_TIMING"))) {
       size_t f = 0, p = 0; for (size_t c = 0; c < nco; c++) { size_t a, b; hip_cohort_stats(m->cohorts[c], &a, &b); f += a; p += b; }
-      fprintf(stderr, "[dp timing] %zu cohorts of <= %zu proofs: %zu merged launches for %zu proof launches\n", nco, csize, f, p);
+      fprintf(stderr, "[dp timing] %zu cohorts of <= %zu proofs in %zu launch groups: %zu merged launches for %zu proof launches (%.0f merged launches per group, %.1f members per launch)\n",
+              nco, csize, ngroups, f, p, ngroups ? (double)f / (double)ngroups : 0.0, f ? (double)p / (double)f : 0.0);
     }
     if (getenv("DP_TIMING") && atoi(getenv("DP_TIMING"))) {
       size_t wpeak = 0; for (auto& w : m->workers) wpeak = std::max(wpeak, hip_dev_arena_peak(w.get()));

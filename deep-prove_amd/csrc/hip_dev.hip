@@ -11,6 +11,7 @@
 #include "gl64_lazy.h"
 #include "sumcheck.h"
 #include "fiber.h"
+#include "cohort.h"
 #include "logup_tail.h"
 #include "axpy_many.h"
 #include "classic_tail.h"
@@ -34,6 +35,7 @@
 #include <type_traits>
 #include <chrono>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <vector>
 #include <string>
@@ -108,120 +110,55 @@ static const bool g_wait_yield = getenv("DP_WAIT_YIELD") && atoi(getenv("DP_WAIT
 static inline void dp_spin_pause() { if (g_wait_yield) sched_yield(); else __builtin_ia32_pause(); }
 
 // ------------------------------------------------------------------------------------------------ cohorts
-// A cohort is a set of proofs of the SAME model proved in lock step on one stream by one host thread (each proof a fiber,
-// fiber.h). Proofs of one model issue the same sequence of launches with the same shapes — only pointers and challenges
-// differ — so launch number i of every member is merged into ONE kc<Body> launch with gridDim.z = members: the per-launch
-// costs of the command processor (dispatch, barrier, end-of-kernel cache maintenance — what bounds a GPU that serves two
-// dozen independent streams of tiny kernels) are paid once per cohort step instead of once per proof step.
-// A member never blocks at a launch: it drops its argument pack and goes on to its next wait (where it yields to the next
-// member); whoever completes a launch's set of packs fires it. Everything is driven from the cohort's one host thread.
+// The lock-step logic lives in cohort.h (struct LaunchGroup: stream, argument-pack ring, the launches being assembled, the fire path — shared by the
+// cohorts that share a hardware queue, one mutex). Here: the group's HIP resources, and the part of a cohort that only its own host thread touches.
+struct HipLaunchGroup : LaunchGroup {
+  static char* ring_alloc(size_t bytes, const char** dev_view) {
+    char* r = nullptr;
+    HIP_CHECK(hipHostMalloc((void**)&r, bytes, host_ro_flags()));
+    HIP_CHECK(hipHostGetDevicePointer((void**)dev_view, r, 0));
+    return r;
+  }
+  static void ring_release(char* r) { hipHostFree(r); }
+  static void* new_stream() { hipStream_t s; HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); return (void*)s; }
+  explicit HipLaunchGroup(size_t ring_bytes) : LaunchGroup(new_stream(), ring_bytes, RingHooks{&ring_alloc, &ring_release}) {}
+  ~HipLaunchGroup() { hipStreamSynchronize((hipStream_t)stream); hipStreamDestroy((hipStream_t)stream); }
+  void drain() { const size_t mark = drain_begin(); HIP_CHECK(hipStreamSynchronize((hipStream_t)stream)); drain_end(mark); }  // (the wait is outside the group's lock)
+};
 struct Cohort {
-  struct Pending {
-    void (*fire)(const Pending&, hipStream_t);  // also the identity of the kernel (one instantiation per Body)
-    const char* name;
-    dim3 g, b; size_t lds, pack_bytes;
-    char* packs; const char* packs_dev;
-    int count, expected;
-    size_t ring_begin, ring_end;
-  };
-  hipStream_t s = nullptr;
-  int members = 0;  // proofs currently in the cohort
-  char* ring = nullptr; const char* ring_dev = nullptr;
-  size_t ring_cap = 0, ring_off = 0;
-  std::deque<Pending> q; size_t q_base = 0;            // q[i] = launch number q_base + i of the common sequence, not yet fired
-  std::deque<std::pair<size_t, size_t>> inflight;      // (launch number, ring_begin) of fired launches not known to have run
-  size_t executed = 0;                                 // every launch number < executed has run to completion
-  size_t nfired = 0, npacks = 0;
-  // DP_TIMING: where a cohort's wall time goes — "device phase" = from a fire to the first member that sees a result afterwards,
-  // "host phase" = from that wake-up to the next fire (the members digest the result one after the other on the cohort's
-  // thread; nothing of this cohort is queued on the GPU meanwhile)
-  std::chrono::steady_clock::time_point t_fire_{}, t_wake_{}; bool awake_ = false, have_fire_ = false;
-  double dev_phase_us = 0, host_phase_us = 0; size_t nwakes = 0;
-  void note_wake() {
-    if (awake_ || !have_fire_) return;
-    awake_ = true; t_wake_ = std::chrono::steady_clock::now(); nwakes++;
-    const double d = std::chrono::duration<double, std::micro>(t_wake_ - t_fire_).count();
-    dev_phase_us += d;
-    if (g_timing_level > 2 && last_fired_) { auto& e = dev_by_[last_fired_]; e.first += d; e.second++; }
-  }
-  // (DP_TIMING=3) host and device phases by the launch that ENDS a host phase / is waited for: where in the proof a cohort's queue stands empty
-  std::map<const char*, std::pair<double, size_t>> host_by_, dev_by_; const char* last_fired_ = nullptr;
-  void note_fire(const char* name = nullptr) {
-    auto t = std::chrono::steady_clock::now();
-    if (awake_) { const double h = std::chrono::duration<double, std::micro>(t - t_wake_).count(); host_phase_us += h; awake_ = false; if (g_timing_level > 2 && name) { auto& e = host_by_[name]; e.first += h; e.second++; } }
-    t_fire_ = t; have_fire_ = true; last_fired_ = name;
-  }
-
-  // `share`: run on the stream of another cohort (which must outlive this one: dp_model_prove_batch keeps the cohorts of a model together). Two cohorts on one
-  // stream take turns on ONE hardware queue: while the members of one digest a result on the host — 21 members x ~65 us on one thread, the queue idle — the
-  // other's launch runs (DP_STREAM_SHARE)
-  bool owns_stream = true;
-  explicit Cohort(size_t ring_bytes = size_t(32) << 20, const Cohort* share = nullptr) : ring_cap(ring_bytes) {
-    if (share) { s = share->s; owns_stream = false; }
-    else HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    HIP_CHECK(hipHostMalloc((void**)&ring, ring_cap, host_ro_flags()));
-    HIP_CHECK(hipHostGetDevicePointer((void**)&ring_dev, ring, 0));
-  }
-  ~Cohort() { if (s) { hipStreamSynchronize(s); if (owns_stream) hipStreamDestroy(s); } if (ring) hipHostFree(ring); }
+  std::shared_ptr<HipLaunchGroup> g;    // the group this cohort launches through in the current batch: its own, or the own group of the group's first cohort
+  std::shared_ptr<HipLaunchGroup> own;  // made when this cohort first leads a group
+  size_t ring_bytes;                    // what this cohort brings to a group's ring
+  explicit Cohort(size_t ring_bytes_ = size_t(32) << 20) : ring_bytes(ring_bytes_) {}  // (no group yet: lead / follow before the first member attaches)
   Cohort(const Cohort&) = delete;
   Cohort& operator=(const Cohort&) = delete;
-
-  // ring space for `bytes` (virtual offsets grow monotonically; physical = virtual mod capacity, regions never straddle
-  // the end), never overlapping a region a launch may still read: those of unfired launches and of fired launches not yet
-  // known to have run
-  size_t ring_take(size_t bytes) {
-    bytes = (bytes + 63) & ~size_t(63);
-    while (!inflight.empty() && inflight.front().first < executed) inflight.pop_front();
-    size_t head = ring_off;
-    if (head % ring_cap + bytes > ring_cap) head += ring_cap - head % ring_cap;
-    size_t tail = !inflight.empty() ? inflight.front().second : !q.empty() ? q.front().ring_begin : head;
-    if (bytes > ring_cap || head + bytes - tail > ring_cap) throw DpError(DP_ERR_OOM, "cohort argument ring exhausted (DP_COHORT_RING_BYTES)");
-    ring_off = head + bytes;
-    return head;
+  // this cohort leads a group of `n` cohorts (itself included) / launches through the group `leader` leads
+  void lead(int n) { if (!own) own = std::make_shared<HipLaunchGroup>(ring_bytes * (size_t)n); own->configure(n, ring_bytes * (size_t)n); g = own; reset_timing(); }
+  void follow(Cohort* leader) { g = leader->own; reset_timing(); }
+  // DP_TIMING: where this cohort's wall time goes — "device phase" = from the last pack its thread dropped to the first of its members that sees a result of
+  // a launch fired since (with several cohorts in a group that includes the wait for the group-mates' packs), "host phase" = from that wake-up to the last pack
+  // dropped before the next one (the members digest the result one after the other on the cohort's thread)
+  std::chrono::steady_clock::time_point t_mark_{}; bool have_submit_ = false; size_t epoch_seen_ = 0;
+  double dev_phase_us = 0, host_phase_us = 0, host_acc_ = 0; size_t nwakes = 0;
+  // (DP_TIMING=3) host and device phases by the launch that ENDS a host phase / is waited for: where in the proof a cohort's queue stands empty
+  std::map<const char*, std::pair<double, size_t>> host_by_, dev_by_; const char* last_submit_ = nullptr;
+  void note_wake() {
+    if (!have_submit_) return;
+    const size_t e = g->fire_epoch.load(std::memory_order_acquire);
+    if (e == epoch_seen_) return;
+    epoch_seen_ = e; nwakes++;
+    auto t = std::chrono::steady_clock::now();
+    const double d = std::chrono::duration<double, std::micro>(t - t_mark_).count();
+    dev_phase_us += d; t_mark_ = t;
+    if (g_timing_level > 2 && last_submit_) { auto& x = dev_by_[last_submit_]; x.first += d; x.second++; if (host_acc_ > 0) { auto& h = host_by_[last_submit_]; h.first += host_acc_; h.second++; } }
+    host_acc_ = 0;
   }
-  // member `li`-th launch of its sequence: add its pack to launch number `li`, fire every launch whose set is complete
-  void submit(size_t li, void (*fire)(const Pending&, hipStream_t), const char* name, dim3 g, dim3 b, size_t lds, const void* pack, size_t pack_bytes) {
-    if (li < q_base) throw DpError(DP_ERR_SHAPE, std::string("cohort out of step: a member reached launch ") + name + " after it was fired (the proofs of a cohort must issue identical launch sequences)");
-    size_t k = li - q_base;
-    if (k > q.size()) throw DpError(DP_ERR_SHAPE, "cohort out of step: launch sequence gap");
-    if (k == q.size()) {
-      Pending p; p.fire = fire; p.name = name; p.g = g; p.b = b; p.lds = lds; p.pack_bytes = pack_bytes; p.count = 0; p.expected = members;
-      p.ring_begin = ring_take(pack_bytes * (size_t)members); p.ring_end = ring_off;
-      p.packs = ring + p.ring_begin % ring_cap; p.packs_dev = ring_dev + p.ring_begin % ring_cap;
-      q.push_back(p);
-    }
-    Pending& p = q[k];
-    if (p.fire != fire || p.g.x != g.x || p.g.y != g.y || p.b.x != b.x || p.lds != lds || p.pack_bytes != pack_bytes)
-      throw DpError(DP_ERR_SHAPE, std::string("cohort out of step: launch ") + name + " of one member meets " + p.name + " of another (the proofs of a cohort must issue identical launch sequences)");
-    if (p.count >= p.expected) throw DpError(DP_ERR_SHAPE, "cohort out of step: too many packs for one launch");
-    memcpy(p.packs + (size_t)p.count * pack_bytes, pack, pack_bytes);
-    p.count++; npacks++;
-    flush();
+  void note_submit(const char* name) {
+    auto t = std::chrono::steady_clock::now();
+    if (have_submit_ && nwakes) { const double h = std::chrono::duration<double, std::micro>(t - t_mark_).count(); host_phase_us += h; host_acc_ += h; }
+    t_mark_ = t; have_submit_ = true; last_submit_ = name;
   }
-  void flush() {
-    while (!q.empty() && q.front().count >= q.front().expected) {
-      Pending& p = q.front();
-      if (p.count > 0) {
-        std::atomic_thread_fence(std::memory_order_release);
-        if (g_host_stats) note_fire(p.name);
-        p.fire(p, s);
-        inflight.push_back({q_base, p.ring_begin});
-        nfired++;
-      }
-      q.pop_front(); q_base++;
-    }
-  }
-  // a member has seen the result of its launch number `li` (or of a later round of it): everything before it has run
-  void note_executed(size_t li) { if (li > executed) executed = li; }
-  int nominal = 0;  // members when the batch started (every member joins before the first launch): what launch shapes may depend on — `members` shrinks while a batch drains
-  void join() { if (!q.empty()) throw DpError(DP_ERR_SHAPE, "a proof cannot join a cohort in the middle of a step"); members++; nominal = members; }
-  // a member leaves (its proofs are done, or it failed) having issued `li` launches: later launches no longer wait for it
-  void leave(size_t li) {
-    members--;
-    for (size_t k = li > q_base ? li - q_base : 0; k < q.size(); k++) q[k].expected--;
-    flush();
-  }
-  void drain() { HIP_CHECK(hipStreamSynchronize(s)); inflight.clear(); executed = q_base; }
+  void reset_timing() { host_by_.clear(); dev_by_.clear(); dev_phase_us = host_phase_us = host_acc_ = 0; nwakes = 0; have_submit_ = false; epoch_seen_ = g ? g->fire_epoch.load() : 0; last_submit_ = nullptr; }
 };
 
 
@@ -278,19 +215,20 @@ class HipDev : public Dev {
   bool queued_() const { return co_ != nullptr; }  // launches are packs handed to someone else: data moves with kernels, never with stream commands
   size_t co_li_ = 0;      // number of launches this member has issued into the cohort's common sequence
   template <auto Body, int MAXT, int FLAGS, class... A>
-  static void fire_(const Cohort::Pending& p, hipStream_t s) {
-    hipLaunchKernelGGL((kc<Body, MAXT, FLAGS, std::decay_t<A>...>), dim3(p.g.x, p.g.y, (unsigned)p.count), p.b, p.lds, s, (const ArgPack<std::decay_t<A>...>*)p.packs_dev);
+  static void fire_(const LaunchGroup::Pending& p, void* s) {
+    hipLaunchKernelGGL((kc<Body, MAXT, FLAGS, std::decay_t<A>...>), dim3(p.gx, p.gy, (unsigned)p.count), dim3(p.bx), p.lds, (hipStream_t)s, (const ArgPack<std::decay_t<A>...>*)p.packs_dev);
   }
   template <auto Body, int MAXT, int FLAGS, class... A, class... P>
   void launch_(KArgs<void (*)(A...)>, const char* name, dim3 g, dim3 b, size_t lds, P... args) {
     static_assert(sizeof...(A) == sizeof...(P), "kernel argument count");
     if (g_host_stats) { if (!first_launch_) first_launch_ = name; last_launch_ = name; by_name_[name]++; }
     if (!co_) { hipLaunchKernelGGL((kg<Body, MAXT, FLAGS, std::decay_t<A>...>), g, b, lds, s_, static_cast<std::decay_t<A>>(args)...); return; }
-    DP_REQUIRE(g.z == 1, DP_ERR_SHAPE, "cohort launches use blockIdx.z for the proof");
+    DP_REQUIRE(g.z == 1 && b.y == 1 && b.z == 1, DP_ERR_SHAPE, "cohort launches use blockIdx.z for the proof and one-dimensional workgroups");
     using Pack = ArgPack<std::decay_t<A>...>;
     static_assert(std::is_trivially_copyable<Pack>::value && std::is_trivially_destructible<Pack>::value, "argument packs travel as bytes");
     Pack pk(static_cast<std::decay_t<A>>(args)...);
-    co_->submit(co_li_++, &fire_<Body, MAXT, FLAGS, A...>, name, g, b, lds, &pk, sizeof(Pack));
+    co_->g->submit(co_li_++, &fire_<Body, MAXT, FLAGS, A...>, name, g.x, g.y, b.x, lds, &pk, sizeof(Pack));
+    if (g_host_stats) co_->note_submit(name);
   }
   template <auto Body, int MAXT, int FLAGS, class... A>
   static void set_lds_(KArgs<void (*)(A...)>, int bytes) {
@@ -356,7 +294,7 @@ class HipDev : public Dev {
         throw DpError(DP_ERR_HIP, std::string("timeout waiting for the device"));
     }
     desc_off_ = 0; stage_off_ = 0;
-    if (co_ && co_li_) co_->note_executed(co_li_ - 1);
+    if (co_ && co_li_) co_->g->note_executed(co_li_ - 1);
     wait_exit_(t0);
   }
   u64* dres_ = nullptr;   // device result buffer
@@ -412,7 +350,7 @@ class HipDev : public Dev {
         std::atomic_thread_fence(std::memory_order_acquire);
         unsigned long long cs = 0;
         for (size_t i = 0; i < nwords; i++) cs += (unsigned long long)(i + 1) * w[i];
-        if (base + cs == tag) { last_tag_ = tag; desc_off_ = 0; stage_off_ = 0; if (co_ && co_li_) co_->note_executed(co_li_ - 1); wait_exit_(t0); return; }
+        if (base + cs == tag) { last_tag_ = tag; desc_off_ = 0; stage_off_ = 0; if (co_ && co_li_) co_->g->note_executed(co_li_ - 1); wait_exit_(t0); return; }
       }
       // inside a fiber the wait hands the host thread to the next proof in flight (fiber.h); otherwise spin
       const bool fib = fiber_active();
@@ -435,7 +373,7 @@ class HipDev : public Dev {
       if (tag != last_tag_) {
         std::atomic_thread_fence(std::memory_order_acquire);
         const unsigned long long cs = logup_tail_checksum(w, block_words);
-        if (base + cs == tag) { last_tag_ = tag; desc_off_ = 0; stage_off_ = 0; if (co_ && co_li_) co_->note_executed(co_li_ - 1); wait_exit_(t0); return; }
+        if (base + cs == tag) { last_tag_ = tag; desc_off_ = 0; stage_off_ = 0; if (co_ && co_li_) co_->g->note_executed(co_li_ - 1); wait_exit_(t0); return; }
       }
       const bool fib = fiber_active();
       if (fib) { nyield_++; fiber_yield(); } else dp_spin_pause();
@@ -887,7 +825,7 @@ class HipDev : public Dev {
           }
         }
         // every chunk has landed: the copy — and everything queued before it — has run
-        desc_off_ = 0; stage_off_ = 0; if (co_ && co_li_) co_->note_executed(co_li_ - 1);
+        desc_off_ = 0; stage_off_ = 0; if (co_ && co_li_) co_->g->note_executed(co_li_ - 1);
         wait_exit_(t0);
       }
       return;
@@ -923,10 +861,11 @@ class HipDev : public Dev {
   // ---- cohort membership (dp_model_prove_batch): while attached every launch of this context is one pack of a merged launch
   void cohort_attach(Cohort* co) {
     DP_REQUIRE(!co_ && !prof_ && zerocopy_, DP_ERR_ARG, "cohort members need the zero-copy publish path and no per-kernel profiling");
+    DP_REQUIRE(co->g != nullptr, DP_ERR_ARG, "a cohort launches through a group: hip_cohort_lead / hip_cohort_follow first");
     HIP_CHECK(hipStreamSynchronize(s_));
-    co->join(); co_ = co; co_li_ = co->q_base;
+    co_li_ = co->g->join(); co_ = co;
   }
-  void cohort_detach() { if (co_) { Cohort* c = co_; co_ = nullptr; c->leave(co_li_); } }
+  void cohort_detach() { if (co_) { Cohort* c = co_; co_ = nullptr; c->g->leave(co_li_); } }
   bool in_cohort() const { return co_ != nullptr; }
   void sync() override { stream_wait(); }
   void flush_uploads() override { if (stage_off_) { stream_wait(); stage_off_ = 0; } }
@@ -1895,8 +1834,7 @@ class HipDev : public Dev {
   size_t merkle_wg_cap_ = [] { const char* e = getenv("DP_MERKLE_WG_CAP"); return e ? (size_t)strtoull(e, nullptr, 10) : size_t(0); }();
   int merkle_grid(size_t nodes) const {
     if (!throughput_mode_ || !merkle_wg_cap_) return grid_for(nodes, 4096);
-    const size_t m = co_ && co_->nominal > 0 ? (size_t)co_->nominal : 1;
-    return grid_for_uncapped(nodes, (int)std::max<size_t>(1, merkle_wg_cap_ / m));
+    return grid_for_uncapped(nodes, (int)member_cap_(merkle_wg_cap_));
   }
   // ---- every grid-stride launch of a cohort member is PLACEABLE AT ONCE (DP_WIDE_WG_CAP, throughput mode). Measured with tools/r06/qprobe.hip
   // (profiles/r06_qprobe.txt): a chain of dependent one-wave kernels on one queue costs 2.8 us per link on an idle chip, 45 us when 22 other queues run
@@ -1908,11 +1846,20 @@ class HipDev : public Dev {
   // Default 256 (round 6, tools/r06/call20.sh, call21.sh: 12 waves of 448 Dense-4M proofs, alternating on one box): 983 / 1 006 / 1 009 / 995 proofs/s with the cap against
   // 937 / 944 / 928 without, 1 034 against 959 at 660 in flight; 192 the same, 128 and 384 less. The hash layers take the same cap (merkle_grid goes through grid_for)
   // unless DP_MERKLE_WG_CAP gives them their own: 512 / 1 024 / 2 048 for them measured 1 037 / 1 023 / 987 against 1 047-1 058 (tools/r06/call24.sh).
+  // A member's share of a cap that is stated per merged launch OF ONE COHORT: a launch group of k cohorts (cohort.h) merges k such launches into one, so its launch
+  // may have k times the workgroups — the sum over all queues stays what round 6 tuned (cohorts x cap), and a member's grid is what it was in a group of one.
+  // DP_GROUP_CAP_X (diagnostic): the factor instead of k.
+  double group_cap_x_ = [] { const char* e = getenv("DP_GROUP_CAP_X"); return e ? std::max(0.0, atof(e)) : 0.0; }();
+  size_t member_cap_(size_t per_cohort_launch) const {
+    if (!co_) return std::max<size_t>(1, per_cohort_launch);
+    const size_t m = co_->g->nominal > 0 ? (size_t)co_->g->nominal : 1;  // (fixed once the batch's members have joined, before the first launch)
+    const double k = group_cap_x_ > 0 && co_->g->ncohorts > 1 ? group_cap_x_ : (double)co_->g->ncohorts;
+    return std::max<size_t>(1, (size_t)((double)per_cohort_launch * k) / m);
+  }
   size_t wide_wg_cap_ = [] { const char* e = getenv("DP_WIDE_WG_CAP"); return e ? (size_t)strtoull(e, nullptr, 10) : size_t(256); }();
   int grid_for(size_t n, int cap = 2048) const {
     if (throughput_mode_ && wide_wg_cap_ && co_) {
-      const size_t m = co_->nominal > 0 ? (size_t)co_->nominal : 1;
-      cap = std::min<int>(cap, (int)std::max<size_t>(1, wide_wg_cap_ / m));
+      cap = std::min<int>(cap, (int)member_cap_(wide_wg_cap_));
     }
     return grid_for_uncapped(n, cap);
   }
@@ -2324,24 +2271,28 @@ class HipDev : public Dev {
 Dev* make_hip_dev(int device) { return new HipDev(device); }
 Dev* make_hip_worker(int device, size_t arena_bytes) { return new HipDev(device, arena_bytes, size_t(16) << 20); }
 // cohorts (lock-step batches of proofs, see struct Cohort): created and driven by dp_model_prove_batch
-Cohort* hip_cohort_new() { const char* e = getenv("DP_COHORT_RING_BYTES"); return e ? new Cohort(strtoull(e, nullptr, 10)) : new Cohort(); }
-Cohort* hip_cohort_new_sharing(Cohort* with) { const char* e = getenv("DP_COHORT_RING_BYTES"); return new Cohort(e ? strtoull(e, nullptr, 10) : size_t(32) << 20, with); }
+static size_t cohort_ring_bytes() { const char* e = getenv("DP_COHORT_RING_BYTES"); return e ? (size_t)strtoull(e, nullptr, 10) : size_t(32) << 20; }
+Cohort* hip_cohort_new() { return new Cohort(cohort_ring_bytes()); }  // (its stream and ring come with the first group it leads: a cohort that only follows owns neither)
+// launch groups of the next batch (between batches only): `c` leads a group of `n` cohorts — ring = the sum of theirs — or launches through the group of `leader`
+void hip_cohort_lead(Cohort* c, size_t n) { c->lead((int)n); }
+void hip_cohort_follow(Cohort* c, Cohort* leader) { c->follow(leader); }
 void hip_cohort_free(Cohort* c) { delete c; }
-void hip_cohort_drain(Cohort* c) { c->drain(); }
+void hip_cohort_drain(Cohort* c) { if (c->g) c->g->drain(); }
+// (fired, packs): the group's counters, reported once — by the cohort that leads it; the DP_TIMING phases are this cohort's own
 void hip_cohort_stats(Cohort* c, size_t* fired, size_t* packs) {
-  *fired = c->nfired; *packs = c->npacks; c->nfired = c->npacks = 0;
-  if (g_host_stats && c->nwakes) fprintf(stderr, "[dp timing] cohort: %zu wake-ups; device phases (fire -> first member sees a result) %.1f ms, host phases (wake-up -> next fire) %.1f ms = %.1f us each\n",
+  *fired = *packs = 0;
+  if (c->g && c->g == c->own) c->g->take_stats(fired, packs);
+  if (g_host_stats && c->nwakes) fprintf(stderr, "[dp timing] cohort: %zu wake-ups; device phases (last pack dropped -> first member sees a result) %.1f ms, host phases (wake-up -> last pack dropped) %.1f ms = %.1f us each\n",
                                         c->nwakes, c->dev_phase_us / 1000.0, c->host_phase_us / 1000.0, c->host_phase_us / c->nwakes);
   if (g_timing_level > 2) {
     for (int which = 0; which < 2; which++) {
       std::vector<std::pair<double, std::string>> v;
       for (auto& kv : which ? c->dev_by_ : c->host_by_) { char b[200]; snprintf(b, sizeof b, "%9.1f ms in %5zu phases, %8.1f us each: %s", kv.second.first / 1000.0, kv.second.second, kv.second.first / kv.second.second, kv.first); v.push_back({kv.second.first, b}); }
       std::sort(v.begin(), v.end(), [](auto& a, auto& b) { return a.first > b.first; });
-      for (size_t i = 0; i < v.size() && i < 14; i++) fprintf(stderr, "[dp cohort %s] %s\n", which ? "device phase ended by the result of" : "host phase before the fire of", v[i].second.c_str());
+      for (size_t i = 0; i < v.size() && i < 14; i++) fprintf(stderr, "[dp cohort %s] %s\n", which ? "device phase ended by the result of" : "host phase before the last pack of", v[i].second.c_str());
     }
   }
-  c->host_by_.clear(); c->dev_by_.clear();
-  c->dev_phase_us = c->host_phase_us = 0; c->nwakes = 0; c->awake_ = false; c->have_fire_ = false;
+  c->reset_timing();
 }
 void hip_dev_cohort_attach(Dev* d, Cohort* c) { static_cast<HipDev*>(d)->cohort_attach(c); }
 void hip_dev_cohort_detach(Dev* d) { static_cast<HipDev*>(d)->cohort_detach(); }
