@@ -100,6 +100,11 @@ inline ModelSpec parse_model(const int64_t* b, size_t n) {
       l.sm_temp_bits = (uint32_t)tb; l.sm_in_scale_bits = (uint32_t)sb; l.sm_table_size = (unsigned)ts; l.sm_zero_chunks = (unsigned)zc; l.sm_zero_vars = (unsigned)zv;
     }
     else if (l.kind == L_GELU) { l.fixed_point_multiplier = rd(); DP_REQUIRE(l.fixed_point_multiplier >= 1 && l.fixed_point_multiplier <= (int64_t(1) << 12), DP_ERR_ARG, "model blob: gelu multiplier"); }  // [17, multiplier = round(2^12 * input scale)]
+    else if (l.kind == L_LOGITS) {  // [18, rows, K]: the argmax over the last dimension of a padded [rows][K] tensor
+      const int64_t r_ = rd(), k_ = rd();
+      DP_REQUIRE(r_ >= 2 && k_ >= 2 && r_ <= (int64_t(1) << 24) && k_ <= (int64_t(1) << 24) && !(r_ & (r_ - 1)) && !(k_ & (k_ - 1)), DP_ERR_ARG, "model blob: logits shape (rows and K are powers of two >= 2)");
+      l.nrows = (size_t)r_; l.ncols = (size_t)k_;
+    }
     else DP_REQUIRE(l.kind == L_RELU || l.kind == L_FLATTEN, DP_ERR_ARG, "model blob: unknown layer kind");
     m.layers.push_back(std::move(l));
   }

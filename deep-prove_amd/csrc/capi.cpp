@@ -210,6 +210,18 @@ int32_t dp_eq_table(dp_ctx* ctx, const uint64_t* point, uint32_t k, dp_buf** out
     *out = new dp_buf{b};
   });
 }
+// TEST ENTRY (not in the public header): Dev::logits_columns (k_logits_cols) on three base-field buffers — the input [rows][K], the row maxima and
+// the chosen indices — into two new buffers the caller frees with dp_buf_free (tests/test_gpu_zzzzzzzzzzzz_logits.py)
+int32_t dp_test_logits_columns(dp_ctx* ctx, const dp_buf* in, const dp_buf* max, const dp_buf* idx, dp_buf** diff_out, dp_buf** onehot_out) {
+  return guard([&] {
+    DP_REQUIRE(ctx && in && max && idx && diff_out && onehot_out && in->b.n, DP_ERR_ARG, "bad arguments");
+    CtxLock lk(ctx);
+    DBuf d = ctx->dev->alloc_persistent(in->b.n, false), o = ctx->dev->alloc_persistent(in->b.n, false);
+    try { ctx->dev->logits_columns(in->b, max->b, idx->b, d, o); ctx->dev->sync(); }
+    catch (...) { ctx->dev->free_persistent(d); ctx->dev->free_persistent(o); throw; }
+    *diff_out = new dp_buf{d}; *onehot_out = new dp_buf{o};
+  });
+}
 int32_t dp_mle_eval(dp_ctx* ctx, const dp_buf* f, const uint64_t* point, uint32_t k, uint64_t out[2]) {
   return guard([&] {
     DP_REQUIRE(ctx && f && point && out, DP_ERR_ARG, "bad arguments");

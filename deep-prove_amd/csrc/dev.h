@@ -125,6 +125,17 @@ class Dev {
     for (size_t r = 0; r < R; r += step) mle_eval_batch(rows.data() + r, (int)std::min(step, R - r), pt, dp_ceil_log2(C), v.data() + r);
     upload(out, (const u64*)v.data());
   }
+  // The two [rows][K] columns of a Logits (argmax) step from its input (base field, row major), the row maxima and the chosen indices (base columns
+  // of `rows` entries): diff[r*K + j] = max[r] - in[r*K + j] (canonical), onehot[r*K + j] = (j == idx[r]). The host then uploads the input once
+  // instead of three columns of its length. Default: download, plain loops, upload; devices override it with one pass.
+  virtual void logits_columns(const DBuf& in, const DBuf& max, const DBuf& idx, const DBuf& diff_out, const DBuf& onehot_out) {
+    const size_t rows = max.n, K = rows ? in.n / rows : 0;
+    DP_REQUIRE(rows && K && in.n == rows * K && idx.n == rows && diff_out.n == in.n && onehot_out.n == in.n && !in.ext && !max.ext && !idx.ext && !diff_out.ext && !onehot_out.ext, DP_ERR_SHAPE, "logits_columns: shapes");
+    std::vector<u64> x(in.n), m(rows), ix(rows), d(in.n), oh(in.n);
+    download(in, x.data()); download(max, m.data()); download(idx, ix.data());
+    for (size_t r = 0; r < rows; r++) for (size_t j = 0; j < K; j++) { d[r * K + j] = gl_sub(m[r], x[r * K + j]); oh[r * K + j] = j == ix[r] ? 1 : 0; }
+    upload(diff_out, d.data()); upload(onehot_out, oh.data());
+  }
   // ---- sumcheck (K1 + K3): fold every table with r (if given; tabs[i] is replaced), then per term the sums
   // sum_b prod_j (v_j[2b] + t (v_j[2b+1] - v_j[2b])) for t = 0..k, written consecutively to `out`.
   virtual void sc_round(DBuf* tabs, int ntabs, const Ext* r, const ScTerm* terms, int nterms, Ext* out) = 0;

@@ -2159,6 +2159,12 @@ class HipDev : public Dev {
     DP_REQUIRE(acc.ext && acc.n == x.n * rep && (rep & (rep - 1)) == 0, DP_ERR_SHAPE, "axpy_rep: shapes");
     nb_ = x.bytes() + 32.0 * acc.n; DPL(k_axpy_rep, dim3(grid_for(acc.n)), dim3(TPB), (Ext*)acc.p, (const void*)x.p, (int)x.ext, coeff, acc.n, dp_ceil_log2(rep));
   }
+  void logits_columns(const DBuf& in, const DBuf& max, const DBuf& idx, const DBuf& diff_out, const DBuf& onehot_out) override {
+    const size_t rows = max.n, K = rows ? in.n / rows : 0;
+    DP_REQUIRE(rows && K && (K & (K - 1)) == 0 && in.n == rows * K && idx.n == rows && diff_out.n == in.n && onehot_out.n == in.n && !in.ext && !max.ext && !idx.ext && !diff_out.ext && !onehot_out.ext, DP_ERR_SHAPE, "logits_columns: shapes");
+    nb_ = 24.0 * in.n;
+    DPL(k_logits_cols, dim3(grid_for(in.n)), dim3(TPB), (const u64*)in.p, (const u64*)max.p, (const u64*)idx.p, (u64*)diff_out.p, (u64*)onehot_out.p, in.n, dp_ceil_log2(K));
+  }
   void bf_round(DBuf& eq, DBuf& f, const Ext* ch, Ext* msg) override {
     DP_REQUIRE(eq.ext && f.ext && eq.n == f.n, DP_ERR_SHAPE, "bf_round: shapes");
     const bool pub = round_ticket_now(TK_CLASSIC, true);

@@ -39,7 +39,7 @@ constexpr uint32_t INFER_ALL_KINDS = 1;  // (DP_INFER_ALL_KINDS of the public he
 constexpr uint32_t INFER_OK = 0, INFER_BAD_REQUANT = 1, INFER_BAD_TOKEN = 2, INFER_BAD_GELU = 3, INFER_BAD_LAYERNORM = 4, INFER_BAD_SOFTMAX = 5;
 // internal only: a LayerNorm's inverse square root input leaves its table (the host has a message of its own for it; INFER_BAD_LAYERNORM in `reasons`)
 constexpr uint32_t INFER_BAD_LAYERNORM_TABLE = 6;
-enum InferOpKind { IO_GEMM = 0, IO_GEMM2, IO_REQUANT, IO_RELU, IO_ADDC, IO_ADD2, IO_EMBED, IO_MAXPOOL, IO_CONV, IO_GELU, IO_LAYERNORM, IO_SOFTMAX, IO_KINDS };
+enum InferOpKind { IO_GEMM = 0, IO_GEMM2, IO_REQUANT, IO_RELU, IO_ADDC, IO_ADD2, IO_EMBED, IO_MAXPOOL, IO_CONV, IO_GELU, IO_LAYERNORM, IO_SOFTMAX, IO_ARGMAX, IO_KINDS };
 // out[b][c*sOc + r*sOr + n*sOn] = sum_m A[b][c*sAc + r*sAr + m*sAm] * B[(B a tensor: b)][c*sBc + m*sBm + n*sBn] (+ bias[n])
 struct InferGemmShape { size_t C = 1, R = 0, K = 0, N = 0; size_t sAc = 0, sAr = 0, sAm = 0, sBc = 0, sBm = 0, sBn = 0, sOc = 0, sOr = 0, sOn = 0; };
 struct InferOp {
@@ -51,7 +51,7 @@ struct InferOp {
   int64_t left = 1, right = 1;       // IO_ADDC: left * x + right * w[i]; IO_ADD2: left * a + right * b; IO_REQUANT, IO_GELU, IO_LAYERNORM: left = multiplier; IO_SOFTMAX: left = scalar, right = bkm
   unsigned shift = 0, bits = 0;      // IO_REQUANT; IO_LAYERNORM: shift = range_check_bits; IO_SOFTMAX: bits = table bits
   // IO_EMBED: vocabulary, embedding size; IO_MAXPOOL: c, h, w; IO_CONV: kw, kx, real_nw, nw, unp_out[3]; IO_GELU: max; IO_LAYERNORM: row length, N;
-  // IO_SOFTMAX: C, R, K, zero chunks, zero vars (in1 = the shift buffer of the chunk, a tensor of C * R words per sample)
+  // IO_SOFTMAX: C, R, K, zero chunks, zero vars (in1 = the shift buffer of the chunk, a tensor of C * R words per sample); IO_ARGMAX: rows, K
   size_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 struct InferProgram {
@@ -74,8 +74,8 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
 
 #ifdef DP_INFER_PLANNER  // (capi.cpp, after zkml.h)
 inline const char* infer_kind_name(int k) {
-  static const char* names[] = {"Dense", "Requant", "ReLU", "Conv", "MaxPool", "Flatten", "MatMul", "Add", "Embeddings", "Positional", "MatMul2", "Add2", "ConcatMatMul", "QKV", "LayerNorm", "Softmax", "Mha", "GELU"};
-  return k >= 0 && k < 18 ? names[k] : "unknown";
+  static const char* names[] = {"Dense", "Requant", "ReLU", "Conv", "MaxPool", "Flatten", "MatMul", "Add", "Embeddings", "Positional", "MatMul2", "Add2", "ConcatMatMul", "QKV", "LayerNorm", "Softmax", "Mha", "GELU", "Logits"};
+  return k >= 0 && k < 19 ? names[k] : "unknown";
 }
 // the shifts of every Softmax row of nb samples, sample by sample over at most DP_HOST_THREADS threads (never more than 16). A sample whose
 // status word is set (any class) was refused by an earlier op: its rows hold whatever the later kernels made of it and are NOT read (no value of
@@ -105,6 +105,7 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
   for (size_t id = 0; id < m.layers.size(); id++) {
     const int k = m.layers[id].kind;
     if ((flags & INFER_ALL_KINDS) && k >= L_LAYERNORM && k <= L_GELU) continue;
+    if (k == L_LOGITS) continue;  // (integer work without tables: inferred under every flag)
     DP_REQUIRE(k >= L_DENSE && k <= L_QKV, DP_ERR_ARG, "dp_model_infer: node " + std::to_string(id) + " is a " + infer_kind_name(k) + " layer (kind " + std::to_string(k) +
                "): LayerNorm, Softmax, Mha and GELU are not inferred on the device yet");
   }
@@ -241,6 +242,9 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
     } else if (l.kind == L_GELU) {
       const TableType tt = gelu_table(l);
       o.kind = IO_GELU; o.table = table_const(tt); o.left = l.fixed_point_multiplier; o.d[0] = size_t(1) << (tt.size - 1); o.out = new_tensor(alen, IQ_NO);
+    } else if (l.kind == L_LOGITS) {  // the index of the first maximum of every row (argmax_rows); reads the int8 copy of a Requant's output where there is one
+      DP_REQUIRE(l.nrows && l.ncols && alen == l.nrows * l.ncols, DP_ERR_SHAPE, "logits: input shape");
+      o.kind = IO_ARGMAX; o.d[0] = l.nrows; o.d[1] = l.ncols; o.out = new_tensor(l.nrows, IQ_NO);
     } else if (l.kind == L_LAYERNORM) {
       const size_t fd = l.weights.size();
       DP_REQUIRE((fd && !(fd & (fd - 1))) && l.bias.size() == fd && alen % fd == 0 && l.ln_dim_size >= 1 && l.ln_dim_size <= fd && l.ln_range_check_bits < 64, DP_ERR_SHAPE, "layernorm: shapes");

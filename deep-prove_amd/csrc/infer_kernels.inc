@@ -226,6 +226,26 @@ __global__ __launch_bounds__(256) void k_infer_softmax(const int64_t* __restrict
   for (unsigned z = 0; z < zc; z++) { acc *= (r & ((int64_t(1) << zv) - 1)) == 0 ? 1 : 0; r >>= zv; }
   o[i] = acc;
 }
+// Logits::Argmax (argmax_rows): one wave per row of K words (rows counts samples x rows of a sample); lanes stride over the row and keep (value,
+// index) under "greater, or equal at a smaller index"; the pairs are reduced across the wave by the same rule, so the result is the FIRST maximum
+// whatever the order of the reduction. Every lane holds a pair: K >= 1, and a lane without an element holds (INT64_MIN, K), which loses against
+// every element. Reads the int8 copy of the input where it has one (the output of a Requant), else the int64 form. No refusal class: any data has an argmax.
+__global__ __launch_bounds__(256) void k_infer_argmax(const int64_t* __restrict__ x64, const int8_t* __restrict__ x8, int64_t* __restrict__ o, size_t rows, size_t K) {
+  const int lane = threadIdx.x & 63;
+  const size_t row = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= rows) return;  // (the whole wave)
+  long long best = INT64_MIN; unsigned long long at = K;
+  for (size_t j = lane; j < K; j += 64) {  // (ascending j: a later equal value never replaces an earlier one)
+    const long long v = x8 ? (long long)x8[row * K + j] : (long long)x64[row * K + j];
+    if (v > best || at == K) { best = v; at = j; }
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const long long ov = __shfl_xor(best, d, 64); const unsigned long long oa = __shfl_xor(at, d, 64);
+    if (ov > best || (ov == best && oa < at)) { best = ov; at = oa; }
+  }
+  if (lane == 0) o[row] = (int64_t)at;
+}
 // model input tensor `off .. off + len` of every sample, from the uploaded block (int8 when the host found every word within -128..127, else int64)
 __global__ __launch_bounds__(256) void k_infer_load(const int64_t* __restrict__ s64, const int8_t* __restrict__ s8, size_t stride, size_t off, size_t len, int64_t* __restrict__ o, int8_t* __restrict__ o8, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -331,6 +351,7 @@ static void infer_launch(const InferProgram& p, const InferOp& o, const InferScr
       break;
     }
     case IO_SOFTMAX: k_infer_softmax<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.in1), c64(o.table), m.T64(o.out), n, o.d[1], o.d[2], o.left, -(((o.right >> 16) + 1) << 16), o.bits, (unsigned)o.d[3], (unsigned)o.d[4], m.status(), len); break;  // (after infer_shift_trip)
+    case IO_ARGMAX: { const size_t rows = nb * o.d[0]; k_infer_argmax<<<infer_grid(rows * 64), 256, 0, s>>>(m.T64(o.in0), m.T8(o.in0), m.T64(o.out), rows, o.d[1]); break; }
     default: throw DpError(DP_ERR_ARG, "dp_model_infer: unknown op");
   }
 }
@@ -414,8 +435,8 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (wall_ms) *wall_ms = ms;
   const size_t n_i8 = launches[IO_KINDS + 2], n_i64 = launches[IO_GEMM] + launches[IO_GEMM2] - n_i8;
-  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu conv %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s\n",
-                   n_i8, n_i64, launches[IO_CONV], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], trips, trip_ms,
+  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu conv %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu argmax %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s\n",
+                   n_i8, n_i64, launches[IO_CONV], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], launches[IO_ARGMAX], trips, trip_ms,
                    ninputs, nchunks, chunk, (double)m.total / 1048576.0, m.in_q ? "int8" : "int64", ms, reasons ? ("; checked, refused " + std::to_string(nrefused)).c_str() : "");
   DP_REQUIRE(!stop, DP_ERR_ARG, INFER_REFUSAL[stop]);
 }

@@ -820,6 +820,17 @@ KBODY k_axpy_rep(Ext* acc, const void* x, int xext, Ext coeff, size_t n_acc, uns
     acc[i] = ex_add(acc[i], m);
   }
 }
+// The two [rows][K] columns of a Logits (argmax) step (Dev::logits_columns) in one pass over its input: diff[i] = max[row] - in[i] (what the range lookup
+// reads; canonical, as gl_sub of canonical operands is) and onehot[i] = (column == idx[row]), K = 2^lg_k. 8 bytes read, 16 written per entry; the `rows`
+// maxima / indices are read through the caches by the K lanes that share them.
+KBODY k_logits_cols(const u64* __restrict__ in, const u64* __restrict__ mx, const u64* __restrict__ idx, u64* __restrict__ diff, u64* __restrict__ onehot, size_t n, unsigned lg_k) {
+  const size_t kmask = (size_t(1) << lg_k) - 1;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = i >> lg_k;
+    diff[i] = gl_sub(mx[row], in[i]);
+    onehot[i] = (i & kmask) == idx[row] ? 1 : 0;
+  }
+}
 // K10 message on evaluation-form pairs: [sum a*ea, sum ((b-a)*ea + a*(eb-ea)), sum (b-a)(eb-ea)]
 // partial[3 * block + {0,1,2}]; `counter` non-null: the last workgroup adds the blocks up and publishes the three sums itself (sc_block_sums_finish)
 __device__ __forceinline__ void bf_msg_acc(Ext a, Ext a1, Ext ea, Ext e1, Ext* c) {

@@ -65,6 +65,8 @@ struct BasefoldProof {
 };
 enum LayerKind { L_DENSE = 0, L_REQUANT = 1, L_RELU = 2, L_CONV = 3, L_MAXPOOL = 4, L_FLATTEN = 5, L_MATMUL = 6, L_ADD = 7, L_EMBED = 8, L_POSITIONAL = 9,
                  L_MATMUL2 = 10, L_ADD2 = 11, L_CONCAT_MATMUL = 12, L_QKV = 13, L_LAYERNORM = 14, L_SOFTMAX = 15, L_MHA = 16, L_GELU = 17 };  // the two-input forms of MatMul / Add, ConcatMatMul, QKV (nodes of a model GRAPH)
+// (the enum lists the kinds the Rust model-blob writer emits, rust/zkml-hip-patch/hip_blob.rs, which mirrors it name by name; Logits is not written there yet)
+constexpr int L_LOGITS = 18;  // Logits::Argmax (layers/transformer/logits.rs)
 struct DenseProof { IOPProof sumcheck; Ext bias_eval; std::vector<Ext> individual_claims; };
 struct AddProof { Ext left_eval = ex_zero(), right_eval = ex_zero(); };  // layers/add.rs:59-63
 struct PositionalProof { std::vector<Ext> sub_matrix_evals; AddProof add_proof; };  // SinglePositionalProof (transformer/positional.rs:45-55), one input
@@ -95,8 +97,10 @@ struct LayerNormProof { std::vector<LogUpProof> logup_proofs; std::vector<Commit
 // SoftmaxProof (layers/transformer/softmax.rs:102-117): lookups (exponential, range, error, zero table if any), commitments, the accumulation and
 // the mask sumcheck, the evaluations exp_in, exp_out, low, high, shift, (zero_in, zero_out)*
 struct SoftmaxProof { std::vector<LogUpProof> logup_proofs; std::vector<Commitment> commitments; IOPProof accumulation_proof, mask_proof; std::vector<Ext> evaluations; };
+// LogitsProof (layers/transformer/logits.rs:62-76), fields in declaration order
+struct LogitsProof { LogUpProof logup_proof; Ext max_eval = ex_zero(); Commitment max_commitment; IOPProof sumcheck_proof; Ext max_mat_eval = ex_zero(); IOPProof hadamard_proof; Ext input_eval = ex_zero(); };
 struct LayerProof { int kind = 0; DenseProof dense; MatMulProof matmul; AddProof add; PositionalProof pos; ActivationProof act; RequantProof req; ConvProof conv; PoolingProof pool; ConcatMatMulProof cmm; QKVProof qkv; LayerNormProof ln; SoftmaxProof sm;
-                    ConcatMatMulProof mha_final, mha_qk; };  // MhaProof {final_mul_proof, softmax_proof, qk_proof} (transformer/mha.rs:122-128) = {mha_final, sm, mha_qk}
+                    ConcatMatMulProof mha_final, mha_qk; LogitsProof logits; };  // MhaProof {final_mul_proof, softmax_proof, qk_proof} (transformer/mha.rs:122-128) = {mha_final, sm, mha_qk}
 struct TableProof { Commitment multiplicity_commit; LogUpProof lookup; };
 struct Proof {
   std::map<size_t, LayerProof> steps;
@@ -197,6 +201,9 @@ inline void serialize_proof_to(const Proof& p, std::vector<u64>& out) {
     } else if (lp.kind == L_MAXPOOL) {
       w.iop(lp.pool.sumcheck); w.logup(lp.pool.lookup); w.ve(lp.pool.zerocheck_evals); w.u(lp.pool.variable_gap);
       w.u(lp.pool.commitments.size()); for (auto& c : lp.pool.commitments) w.comm(c);
+    } else if (lp.kind == L_LOGITS) {
+      const LogitsProof& q = lp.logits;
+      w.logup(q.logup_proof); w.e(q.max_eval); w.comm(q.max_commitment); w.iop(q.sumcheck_proof); w.e(q.max_mat_eval); w.iop(q.hadamard_proof); w.e(q.input_eval);
     } else DP_REQUIRE(false, DP_ERR_ARG, "serialize_proof: unknown layer kind");
   }
   w.u(p.table_proofs.size()); for (auto& tp : p.table_proofs) { w.comm(tp.multiplicity_commit); w.logup(tp.lookup); }
@@ -296,6 +303,9 @@ inline Proof deserialize_proof(const u64* words, size_t n) {
     } else if (lp.kind == L_MAXPOOL) {
       lp.pool.sumcheck = r.iop(); lp.pool.lookup = r.logup(); lp.pool.zerocheck_evals = r.ve(); lp.pool.variable_gap = (size_t)r.u();
       size_t k = r.len(); lp.pool.commitments.resize(k); for (auto& c : lp.pool.commitments) c = r.comm();
+    } else if (lp.kind == L_LOGITS) {
+      LogitsProof& q = lp.logits;
+      q.logup_proof = r.logup(); q.max_eval = r.e(); q.max_commitment = r.comm(); q.sumcheck_proof = r.iop(); q.max_mat_eval = r.e(); q.hadamard_proof = r.iop(); q.input_eval = r.e();
     } else DP_REQUIRE(false, DP_ERR_ARG, "proof stream: unknown layer kind");
     p.steps[id] = lp;
   }

@@ -79,6 +79,9 @@ struct LayerSpec {
   // [seq][heads][head_dim] — that bundles qk = ConcatMatMul (1,2,0) x (1,2,0) -> [heads][seq][seq], the Softmax described by the sm_* fields
   // (sm_shape unused) straight on the products, final_mul = ConcatMatMul (0,2,1) x (1,0,2), permuted (1,0,2) -> [seq][heads][head_dim]
   size_t mha_shape[3] = {0, 0, 0};  // seq, heads, head_dim
+  // logits (layers/transformer/logits.rs, Logits::Argmax): the input is a padded [nrows = rows][ncols = K] tensor, the output the `rows` indices of
+  // the first maximum of every row. The argmax runs over the PADDED row (logits.rs:90-125 ignores the unpadded shapes): a front end that pads a
+  // vocabulary must keep its padding columns from winning. Only as the model's single output tensor (verify_output_evaluation, logits.rs:693-731).
   unsigned right_shift = 0, fp_scale = 0, intermediate_bit_size = 0;
   int64_t fixed_point_multiplier = 0;
   unsigned shift() const { return fp_scale + right_shift; }
@@ -342,8 +345,10 @@ struct ConvTrace {
 // per node: first input, first output; in2 = second input of a two-input node; more_out = the outputs after the first (QKV: K, V)
 // MhaData (mha.rs:45-52): the products Q K^T the softmax reads and the probabilities final_mul reads (its output is the node's: final_reshape moves nothing)
 struct MhaTrace { std::vector<int64_t> softmax_in, softmax_out; };
+// ArgmaxData (logits.rs:48-51): the row maxima of every Logits node (its output holds the indices)
 struct Trace {
   std::vector<std::vector<int64_t>> in, out, in2, in3; std::vector<std::vector<std::vector<int64_t>>> more_out; std::vector<ConvTrace> conv; std::map<size_t, MhaTrace> mha;
+  std::map<size_t, std::vector<int64_t>> argmax_max;
   const std::vector<int64_t>& tensor(int node, int slot) const { return slot == 0 ? out[(size_t)node] : more_out[(size_t)node][(size_t)slot - 1]; }
 };
 // FFT of every kernel of a convolution, zero-padded to 2 nw^2 (index_w, tensor.rs:236-254): computed once per model —
@@ -442,6 +447,7 @@ inline void tensor_lens(const ModelSpec& m, std::vector<size_t>& lens, std::vect
     else if (l.kind == L_CONV) cur = l.kw * l.nw * l.nw;
     else if (l.kind == L_MAXPOOL) cur = l.pin[0] * (l.pin[1] / 2) * (l.pin[2] / 2);
     else if (l.kind == L_CONCAT_MATMUL) { const CmShape g = cm_shape(l); cur = g.out[0] * g.out[1] * g.out[2]; }
+    else if (l.kind == L_LOGITS) cur = l.nrows;
     lens[id] = cur;
   }
 }
@@ -519,6 +525,17 @@ inline std::vector<int64_t> concat_matmul_op(const LayerSpec& l, const std::vect
     if (l.cm_perm.empty()) o = std::move(r);
     else { const size_t rs[3] = {g.C, g.R, g.N}; const int po[3] = {l.cm_perm[0], l.cm_perm[1], l.cm_perm[2]}; o = transpose3(r, rs, po); }
   return o;
+}
+// max_in_slice (zkml/src/lib.rs:194-206) on every row of a [rows][K] tensor: a fold from (MIN, 0) that moves on a STRICTLY greater value — the index
+// of the first maximum, 0 for a row of equal values
+inline std::vector<int64_t> argmax_rows(const std::vector<int64_t>& x, size_t rows, size_t K, std::vector<int64_t>& maxima) {
+  std::vector<int64_t> idx(rows); maxima.resize(rows);
+  for (size_t r = 0; r < rows; r++) {
+    int64_t best = INT64_MIN; size_t at = 0;
+    for (size_t j = 0; j < K; j++) if (x[r * K + j] > best) { best = x[r * K + j]; at = j; }
+    idx[r] = (int64_t)at; maxima[r] = best;
+  }
+  return idx;
 }
 inline Trace run_model(const ModelSpec& m, const std::vector<int64_t>& input) {
   Trace tr;
@@ -624,6 +641,10 @@ inline Trace run_model(const ModelSpec& m, const std::vector<int64_t>& input) {
     else if (l.kind == L_CONV) { tr.conv.resize(m.layers.size()); o = conv_op(l, cur, tr.conv[tr.in.size() - 1]); }
     else if (l.kind == L_MAXPOOL) o = maxpool_op(l, cur);
     else if (l.kind == L_FLATTEN) o = cur;
+    else if (l.kind == L_LOGITS) {  // Logits::evaluate_with_argmax_data (logits.rs:90-125)
+      DP_REQUIRE(l.nrows && l.ncols && cur.size() == l.nrows * l.ncols, DP_ERR_SHAPE, "logits: input shape");
+      o = argmax_rows(cur, l.nrows, l.ncols, tr.argmax_max[id]);
+    }
     else DP_REQUIRE(false, DP_ERR_ARG, "unknown layer kind");
     tr.out.push_back(std::move(o));
   }
@@ -697,6 +718,14 @@ inline void validate_model(const ModelSpec& m) {
   std::vector<size_t> lens, in_len, in2_len, in3_len;
   tensor_lens(m, lens, &in_len, &in2_len, &in3_len);
   for (const Edge& e : output_edges(m)) DP_REQUIRE(e.from >= 0 && (size_t)e.from < m.layers.size() && e.slot >= 0 && (size_t)e.slot < out_degree(m.layers[(size_t)e.from]), DP_ERR_SHAPE, "model graph: output edge");
+  // a Logits node is checked against io.output by the verifier itself, which wants exactly one output tensor (verify_output_evaluation, logits.rs:693-701):
+  // its output is the model's only output tensor and no node reads it
+  for (size_t id = 0; id < m.layers.size(); id++) if (m.layers[id].kind == L_LOGITS) {
+    const std::vector<Edge> outs = output_edges(m);
+    bool read = false;
+    for (size_t q = 0; q < m.layers.size(); q++) for (const Edge& e : edges_in(m, q)) read = read || e.from == (int)id;
+    DP_REQUIRE(outs.size() == 1 && outs[0].from == (int)id && outs[0].slot == 0 && !read, DP_ERR_ARG, "node " + std::to_string(id) + " (kind 18, logits): its output must be the model's only output tensor, read by no node");
+  }
   for (size_t id = 0; id < m.layers.size(); id++) for (size_t j = 0; j < out_degree(m.layers[id]); j++) reader_of(m, (int)id, (int)j);  // exactly one reader each
   { std::vector<size_t> ins = input_tensor_lens(m); for (size_t q = 0; q < ins.size(); q++) reader_of(m, -1, (int)q); }
   auto check_softmax = [](const LayerSpec& l, size_t cur) {
@@ -775,6 +804,11 @@ inline void validate_model(const ModelSpec& m) {
       DP_REQUIRE(is_pow2(l.pin[0]) && is_pow2(l.pin[1]) && is_pow2(l.pin[2]) && l.pin[1] >= 2 && l.pin[2] >= 4 && cur == l.pin[0] * l.pin[1] * l.pin[2] && cur >= 16, DP_ERR_SHAPE, "maxpool: padded input shape");
       cur /= 4;
     } else if (l.kind == L_FLATTEN) {}
+    else if (l.kind == L_LOGITS) {
+      const std::string who = "node " + std::to_string(id) + " (kind 18, logits): ";
+      DP_REQUIRE(is_pow2(l.nrows) && is_pow2(l.ncols) && l.nrows >= 2 && l.ncols >= 2 && l.nrows <= (size_t(1) << 24) && l.ncols <= (size_t(1) << 24), DP_ERR_ARG, who + "rows and K must be powers of two >= 2");
+      DP_REQUIRE(cur == l.nrows * l.ncols, DP_ERR_ARG, who + "the input must have rows * K entries");
+    }
     else DP_REQUIRE(false, DP_ERR_ARG, "unknown layer kind");
   }
 }
@@ -798,6 +832,7 @@ inline std::unique_ptr<Context> context_generate(Dev& dev, const ModelSpec& m) {
     else if (l.kind == L_RELU) { add({0, 0}); mpl = std::max(mpl, next_pow2(cur)); }
     else if (l.kind == L_GELU) { add(gelu_table(l)); mpl = std::max(mpl, next_pow2(cur)); }
     else if (l.kind == L_MAXPOOL) { add({2, 0}); mpl = std::max(mpl, next_pow2(cur)); }
+    else if (l.kind == L_LOGITS) { add({2, 0}); mpl = std::max(mpl, next_pow2(cur)); }  // (the committed polynomial is the vector of maxima, as long as the output; logits.rs:242)
     else if (l.kind == L_LAYERNORM) { add({2, 0}); add(layernorm_table(l)); mpl = std::max(mpl, next_pow2(cur)); }  // layernorm.rs:587-618
     else if (l.kind == L_SOFTMAX) { add({2, 0}); add(softmax_table(l)); add(softmax_error_table(l)); if (l.sm_zero_vars) add({6, l.sm_zero_vars}); mpl = std::max(mpl, next_pow2(cur)); }  // softmax.rs:1205-1245
   }
@@ -914,6 +949,8 @@ struct ProverState {
   std::map<size_t, DBuf> staged_in, staged_out;
   std::map<size_t, SoftmaxTrace> sm_trace;    // SoftmaxData of every Softmax node, likewise
   std::map<size_t, LayerNormTrace> ln_trace;  // LayerNormData of every LayerNorm node (kept from the witness generation for its prover)
+  struct LogitsDev { DBuf in, onehot; };       // the input of every Logits node and the one-hot matrix of its output (base columns, instantiate_witness_ctx)
+  std::map<size_t, LogitsDev> logits_dev;
   void add_witness_claim(const DevCommit& c, Claim cl) {
     if (c.nv <= PCS_BASECODE_LOG) trivial_claims.push_back({c, std::move(cl)}); else claims.push_back({c, std::move(cl)});
   }
@@ -945,7 +982,9 @@ struct WitnessHost {
   struct Col { std::vector<int64_t> v; };
   // col_ids: committed columns, in commit order; the first n_lookup_cols of them (all, if 0) are the lookup's columns. late >= 0: the lookup's
   // only column is `lates[late]`, a column that is NOT committed (Softmax's row sums), and every committed column is an extra one
-  struct Pending { size_t node; int which; std::vector<size_t> col_ids; size_t cpi; TableType tt; size_t n_lookup_cols = 0; int late = -1; };
+  // logits_in >= 0 (a Logits node): the lookup's only column is MADE ON THE DEVICE (Dev::logits_columns) from lates[logits_in], the node's input, the
+  // committed column (the row maxima) and lates[logits_idx], the chosen indices; the committed column is an extra one
+  struct Pending { size_t node; int which; std::vector<size_t> col_ids; size_t cpi; TableType tt; size_t n_lookup_cols = 0; int late = -1; int logits_in = -1, logits_idx = -1; };
   struct TabInfo { TableType tt; std::vector<size_t> col_ids; std::vector<u64> mult; };
   struct Act { size_t node; bool is_out; size_t n; size_t off; };
   std::vector<Pending> pend; std::vector<size_t> late_ids; std::vector<TabInfo> tabs; std::vector<Act> acts;
@@ -1066,6 +1105,19 @@ inline WitnessHost witness_host(const Context& ctx, const Trace& tr) {
       p.col_ids.push_back(cols.size()); cols.push_back({tr.out[id]});  // committed, but not a lookup column
       p.n_lookup_cols = 4;
       pend.push_back(p);
+    } else if (l.kind == L_LOGITS) {  // Logits::gen_lookup_witness (logits.rs:474-552): the maxima are committed, max - input is looked up in the range table
+      const std::vector<int64_t>& x = tr.in[id]; const std::vector<int64_t>& mx = tr.argmax_max.at(id);
+      const size_t K = l.ncols;
+      DP_REQUIRE(x.size() == mx.size() * K && tr.out[id].size() == mx.size(), DP_ERR_SHAPE, "logits: trace shapes");
+      for (size_t i = 0; i < x.size(); i++) {
+        const int64_t d = mx[i / K] - x[i];  // (>= 0: mx is the row's maximum)
+        DP_REQUIRE(d < (int64_t(1) << Q_BIT_LEN), DP_ERR_ARG, "logits: a row spreads beyond the range table");
+        count_range(d);
+      }
+      Pending p{id, 0, {cols.size()}, 1, TableType{2, 0}}; cols.push_back({mx});
+      p.logits_in = (int)lates.size(); lates.push_back(x);
+      p.logits_idx = (int)lates.size(); lates.push_back(tr.out[id]);
+      pend.push_back(p);
     }
   }
   wh.n_witness_cols = cols.size();
@@ -1140,6 +1192,13 @@ inline void instantiate_witness_ctx(ProverState& ps, const Trace& tr, WitnessHos
       w.commits.push_back(comms[cid]);
     }
     if (p.late >= 0) w.columns.push_back(dcol[late_ids[(size_t)p.late]]);
+    if (p.logits_in >= 0) {  // (the arena allocations of a proof live until prove() releases its mark)
+      const DBuf in = dcol[late_ids[(size_t)p.logits_in]], mx = dcol[p.col_ids.at(0)];
+      DBuf diff = dev.alloc(in.n, false), onehot = dev.alloc(in.n, false);
+      dev.logits_columns(in, mx, dcol[late_ids[(size_t)p.logits_idx]], diff, onehot);
+      w.columns = {diff}; w.extra_columns = {mx};
+      ps.logits_dev[p.node] = {in, onehot};
+    }
     ps.lookup_witness[p.node].push_back(std::move(w));
   }
   for (size_t i = 0; i < tabs.size(); i++) {
@@ -1943,6 +2002,59 @@ inline Claim prove_pooling(ProverState& ps, size_t id, const LayerSpec& l, const
   return next;
 }
 
+// Logits::prove, Argmax (layers/transformer/logits.rs:306-472). The lookup shows max[i] - x[i][j] in 0..255 for every entry (the maximum bounds its
+// row); what remains is that the maximum is ATTAINED at the claimed index: with M[i][j] = max[i] * [j == idx[i]], a first sumcheck over the columns
+// turns the committed maxima at the row point into M at (s1 | row point), and the second one proves M = input o onehot there, batched (by a challenge
+// drawn after the lookup's claim is absorbed) with the lookup's own claim on the input. The claim `last` that prove() drew on the output tensor is
+// drawn and NOT used, as in the reference (`_last_claims`): the verifier evaluates the one-hot matrix of io.output itself.
+// The second sumcheck lists `input` once per product in the reference (two Arcs of one polynomial): here the table is shared — the round messages are
+// sums over the same values and final evaluation [0] is the input's either way.
+inline Claim prove_logits(ProverState& ps, size_t id, const LayerSpec& l, const std::vector<int64_t>& output, const std::vector<int64_t>& maxima) {
+  Dev& dev = *ps.dev; Transcript& t = *ps.t;
+  std::vector<LogUpWitness>& ws = ps.lookup_witness.at(id);
+  DP_REQUIRE(ws.size() == 1 && ws[0].columns.size() == 1 && ws[0].commits.size() == 1, DP_ERR_ARG, "logits: lookup witness shape");
+  const ProverState::LogitsDev& ld = ps.logits_dev.at(id);
+  const size_t rows = l.nrows, K = l.ncols, n = rows * K;
+  const unsigned nvr = dp_ceil_log2(rows), nvk = dp_ceil_log2(K), nv = nvr + nvk;
+  DP_REQUIRE(output.size() == rows && maxima.size() == rows && ld.in.n == n, DP_ERR_SHAPE, "logits: shapes");
+  LogitsProof pr;
+  pr.logup_proof = logup_batch_prove(dev, ps.logup_input(ws[0]), t);
+  const Claim diff_claim = pr.logup_proof.output_claims.at(0);
+  DP_REQUIRE(diff_claim.point.size() == nv, DP_ERR_SHAPE, "logits: lookup claim point");
+  const std::vector<Ext> row_point(diff_claim.point.begin() + nvk, diff_claim.point.end());  // split_claim_point: the rows are the most significant variables
+  std::vector<Ext> mx(rows); for (size_t i = 0; i < rows; i++) mx[i] = ex_from_i64(maxima[i]);
+  pr.max_eval = host_mle_eval(mx, row_point);
+  pr.max_commitment = pure_commitment(ws[0].commits[0]);
+  ps.add_witness_claim(ws[0].commits[0], {row_point, pr.max_eval});
+  const Claim input_claim{diff_claim.point, ex_sub(pr.max_eval, diff_claim.eval)};
+  size_t mk = dev.mark();
+  {  // the sparse matrix M with its row variables fixed at row_point: `rows` terms, made on the host
+    const std::vector<Ext> beta = host_eq_table(row_point);
+    std::vector<Ext> reduced(K, ex_zero());
+    for (size_t i = 0; i < rows; i++) { DP_REQUIRE(output[i] >= 0 && (size_t)output[i] < K, DP_ERR_SHAPE, "logits: index outside the row"); reduced[(size_t)output[i]] = ex_add(reduced[(size_t)output[i]], ex_mul(beta[i], mx[i])); }
+    DevVP vp(nvk);
+    vp.add_mle_list({upload_exts(dev, reduced), upload_exts(dev, std::vector<Ext>(K, ex_one()))}, ex_one());
+    SumcheckOut sc = sumcheck_prove(dev, vp, t);
+    pr.sumcheck_proof = sc.proof; pr.max_mat_eval = sc.finals[0];
+  }
+  dev.release(mk);
+  std::vector<Ext> claim_point = pr.sumcheck_proof.point; claim_point.insert(claim_point.end(), row_point.begin(), row_point.end());
+  t.append_exts(input_claim.point); t.append_ext(input_claim.eval);  // squeeze_challenge (logits.rs:147-156)
+  const Ext challenge = t.read_challenge();
+  {
+    DBuf beta = dev.alloc(n, true), input_eq = dev.alloc(n, true);
+    std::vector<EqAcc> eqs = {{beta, claim_point, ex_one(), false}, {input_eq, input_claim.point, ex_one(), false}};
+    DevVP vp(nv);
+    vp.add_mle_list({ld.in, ld.onehot, beta}, ex_one());
+    vp.add_mle_list({input_eq, ld.in}, challenge);
+    SumcheckOut sc = sumcheck_prove_with_eq(dev, eqs, vp, t);
+    pr.hadamard_proof = sc.proof; pr.input_eval = sc.finals[0];
+  }
+  dev.release(mk);
+  LayerProof lp; lp.kind = L_LOGITS; lp.logits = pr; ps.proofs[id] = lp;
+  return {pr.hadamard_proof.point, pr.input_eval};
+}
+
 // Prover::prove(trace). `tr` comes from run_model (inference is not part of proving time in the reference either).
 // `dev` may be any device context on the GPU that holds `ctx` (the model commitments are only read), so several proofs
 // can be in flight at once, each on its own stream/arena (dp_model_prove_batch).
@@ -2007,6 +2119,7 @@ inline Proof prove(Context& ctx, Dev& dev, const Trace& tr, Transcript& t, Witne
     else if (l.kind == L_SOFTMAX) cur = prove_softmax(ps, id, l, cur);
     else if (l.kind == L_CONV) cur = prove_conv(ps, id, l, cur, tr.conv.at(id));
     else if (l.kind == L_MAXPOOL) cur = prove_pooling(ps, id, l, cur);
+    else if (l.kind == L_LOGITS) cur = prove_logits(ps, id, l, tr.out[id], tr.argmax_max.at(id));
     // L_FLATTEN is not provable: the claim passes through unchanged (iop/prover.rs:449-456)
     if (pt.on) { char b[64]; snprintf(b, sizeof b, "layer %zu (kind %d)", id, l.kind); pt.lap(b); }
     made[id] = {cur};
@@ -2058,6 +2171,7 @@ inline void verify(const VerifierContext& vc, const Proof& proof, const IO& io, 
     if (it->second.kind == L_RELU || it->second.kind == L_GELU) add_fracs(it->second.act.lookup);
     if (it->second.kind == L_REQUANT) { add_fracs(it->second.req.clamping_lookup); add_fracs(it->second.req.shifted_lookup); }
     if (it->second.kind == L_MAXPOOL) add_fracs(it->second.pool.lookup);
+    if (it->second.kind == L_LOGITS) add_fracs(it->second.logits.logup_proof);
     if (it->second.kind == L_LAYERNORM) for (auto& lg : it->second.ln.logup_proofs) add_fracs(lg);
     if (it->second.kind == L_SOFTMAX || it->second.kind == L_MHA) for (auto& lg : it->second.sm.logup_proofs) add_fracs(lg);
   }
@@ -2313,6 +2427,43 @@ inline void verify(const VerifierContext& vc, const Proof& proof, const IO& io, 
       for (size_t i = 0; i < ks; i++) next.eval = ex_add(next.eval, ex_mul(ex_sub(output_eval, pp.zerocheck_evals[i]), mult[i]));
       cur = next;
       cur_len *= 4;
+    } else if (l.kind == L_LOGITS) {  // LogitsCtx::verify (logits.rs:580-730). The output claim `cur` was drawn where the prover drew it and is dropped.
+      const LogitsProof& gp = lp.logits;
+      TableType rt{2, 0};
+      DP_REQUIRE(chmap.count(rt), DP_ERR_VERIFY, "logits: no challenge for the range table");
+      LogUpVerifierClaim vcl = verify_logup_proof(gp.logup_proof, 1, constant_challenge, chmap[rt], t, 0);
+      const size_t rows = l.nrows, K = l.ncols;
+      const unsigned nvr = dp_ceil_log2(rows), nvk = dp_ceil_log2(K), nv = nvr + nvk;
+      DP_REQUIRE(is_pow2(rows) && is_pow2(K) && rows >= 2 && K >= 2 && in_lens[id] == rows * K && vcl.claims.size() == 1 && vcl.claims[0].point.size() == nv, DP_ERR_VERIFY, "logits: shapes");
+      const Claim& dc = vcl.claims[0];
+      const std::vector<Ext> row_point(dc.point.begin() + nvk, dc.point.end());
+      const Claim input_claim{dc.point, ex_sub(gp.max_eval, dc.eval)};
+      add_claim(gp.max_commitment, {row_point, gp.max_eval});
+      // the vector of maxima -> the sparse matrix of maxima: the second factor is the all-ones table, which evaluates to 1 everywhere
+      SubClaim s1 = sumcheck_verify(gp.max_eval, gp.sumcheck_proof, nvk, 2, t);
+      DP_REQUIRE(ex_eq(s1.expected_evaluation, gp.max_mat_eval), DP_ERR_VERIFY, "logits: sparse-matrix sumcheck evaluation failed");
+      std::vector<Ext> claim_point = s1.point; claim_point.insert(claim_point.end(), row_point.begin(), row_point.end());
+      t.append_exts(input_claim.point); t.append_ext(input_claim.eval);  // squeeze_challenge (logits.rs:147-156)
+      const Ext challenge = t.read_challenge();
+      SubClaim s2 = sumcheck_verify(ex_add(gp.max_mat_eval, ex_mul(challenge, input_claim.eval)), gp.hadamard_proof, nv, 3, t);
+      const Ext beta_eval = identity_eval(claim_point, s2.point), input_eq_eval = identity_eval(input_claim.point, s2.point);
+      const Ext divisor = ex_mul(beta_eval, gp.input_eval);
+      DP_REQUIRE(!ex_is_zero(divisor), DP_ERR_VERIFY, "logits: zero divisor in the output evaluation");
+      const Ext expected_output_eval = ex_mul(ex_sub(s2.expected_evaluation, ex_mul(ex_mul(challenge, gp.input_eval), input_eq_eval)), ex_inv(divisor));
+      // verify_output_evaluation (logits.rs:693-731): the one-hot matrix of the tokens of io.output — the model's only output tensor — at s2's point
+      DP_REQUIRE(output_edges(m).size() == 1 && output_edges(m)[0].from == (int)id && io.output.size() == rows, DP_ERR_VERIFY, "logits: the node's output must be the model's only output tensor");
+      const std::vector<Ext> col_pt(s2.point.begin(), s2.point.begin() + nvk), row_pt(s2.point.begin() + nvk, s2.point.end());
+      const std::vector<Ext> beta = host_eq_table(row_pt);
+      Ext computed = ex_zero();
+      for (size_t i = 0; i < rows; i++) {
+        DP_REQUIRE(io.output[i] >= 0 && (uint64_t)io.output[i] < K, DP_ERR_VERIFY, "logits: token outside the row");
+        Ext sel = beta[i];
+        for (unsigned b = 0; b < nvk; b++) sel = ex_mul(sel, ((io.output[i] >> b) & 1) ? col_pt[b] : ex_sub(ex_one(), col_pt[b]));
+        computed = ex_add(computed, sel);
+      }
+      DP_REQUIRE(ex_eq(computed, expected_output_eval), DP_ERR_VERIFY, "logits: output claim evaluation check failed");
+      cur = {s2.point, gp.input_eval};
+      cur_len = rows * K;
     } else if (l.kind == L_DENSE) {  // DenseCtx::verify_dense (dense.rs:576-643)
       const DenseProof& dpf = lp.dense;
       DP_REQUIRE(cur.point.size() == dp_ceil_log2(l.nrows) && dpf.individual_claims.size() == 2, DP_ERR_VERIFY, "dense: shapes");
@@ -2727,7 +2878,8 @@ inline VerifierContext vctx_from_words(const u64* w, size_t n) {
     l.kw = (size_t)rd(); l.kx = (size_t)rd(); l.real_nw = (size_t)rd(); l.nw = (size_t)rd();
     for (int k = 0; k < 3; k++) l.unp_out[k] = (size_t)rd();
     for (int k = 0; k < 3; k++) l.pin[k] = (size_t)rd();
-    DP_REQUIRE(l.kind >= L_DENSE && l.kind <= L_GELU, DP_ERR_ARG, "verifier blob: layer kind");
+    DP_REQUIRE(l.kind >= L_DENSE && l.kind <= L_LOGITS, DP_ERR_ARG, "verifier blob: layer kind");
+    if (l.kind == L_LOGITS) DP_REQUIRE(is_pow2(l.nrows) && is_pow2(l.ncols) && l.nrows >= 2 && l.ncols >= 2 && l.nrows <= (size_t(1) << 24) && l.ncols <= (size_t(1) << 24), DP_ERR_ARG, "verifier blob: logits shape");
     if (l.kind == L_GELU) DP_REQUIRE(l.fixed_point_multiplier >= 1 && l.fixed_point_multiplier <= (int64_t(1) << 12), DP_ERR_ARG, "verifier blob: gelu multiplier");
     if (l.kind == L_MHA) {
       l.sm_table_size = l.right_shift; l.sm_zero_chunks = l.fp_scale; l.sm_scalar = l.fixed_point_multiplier; l.sm_temp_bits = (uint32_t)l.intermediate_bit_size;

@@ -7,6 +7,7 @@ import numpy as np
 
 L_DENSE, L_REQUANT, L_RELU, L_CONV, L_MAXPOOL, L_FLATTEN, L_MATMUL, L_ADD, L_EMBED, L_POSITIONAL = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 L_LAYERNORM, L_SOFTMAX, L_MHA, L_GELU = 14, 15, 16, 17
+L_LOGITS = 18  # Logits::Argmax (layers/transformer/logits.rs): the last node of a language model
 L_MATMUL2, L_ADD2, L_CONCAT_MATMUL, L_QKV = 10, 11, 12, 13  # nodes of a model GRAPH: two-input MatMul / Add, ConcatMatMul, QKV
 BIT_LEN = 8
 FIXED_POINT_SCALE = 25  # zkml/src/layers/requant.rs:47
@@ -193,6 +194,12 @@ def layernorm_apply(l, x):
     inv = inv_sqrt_table_output(l["eps_bits"], l["range_check_bits"], lin)
     out = l["gamma"][None, :] * (l["dim_size"] * rows - s[:, None]) * inv[:, None] + l["beta"][None, :]
     return out.reshape(-1), (lin, inv, full & ((1 << l["range_check_bits"]) - 1))
+
+
+def logits_apply(l, x):
+    """Logits::Argmax on quantised values (layers/transformer/logits.rs:90-125, max_in_slice): per row of the PADDED [rows][K] tensor the index of the
+    FIRST maximum (np.argmax's rule) -> the `rows` chosen tokens"""
+    return np.asarray(x, dtype=np.int64).reshape(l["rows"], l["K"]).argmax(axis=1).astype(np.int64)
 
 
 def dense_output_bitsize(ncols):
@@ -410,6 +417,18 @@ class ModelBuilder:
         self._cur = int(np.prod(self.shape_pad))
         return self
 
+    def logits(self):
+        """Logits::Argmax (layers/transformer/logits.rs) over the last dimension of the padded [rows][K] activation: the model's output becomes
+        the `rows` chosen tokens. The last layer of a model; its input must come out of a Requant in practice (max - x is looked up in the
+        256-entry range table). The argmax runs over the PADDED row, as the reference's: padding columns must not be able to win."""
+        assert len(self.shape_pad) == 2, "logits needs a [rows, K] activation"
+        rows, k = self.shape_pad
+        assert rows >= 2 and k >= 2 and rows * k == self._cur
+        self.layers.append(dict(kind=L_LOGITS, rows=rows, K=k))
+        self.shape_og, self.shape_pad = (self.shape_og[0],), (rows,)
+        self._cur = rows
+        return self
+
     def flatten(self):
         self._garbage = (self.shape_og, self.shape_pad)
         self.layers.append(dict(kind=L_FLATTEN))
@@ -454,6 +473,8 @@ class ModelBuilder:
                 parts.append(l["beta"])
             elif l["kind"] == L_GELU:
                 parts.append(np.array([L_GELU, l["multiplier"]], dtype=np.int64))
+            elif l["kind"] == L_LOGITS:
+                parts.append(np.array([L_LOGITS, l["rows"], l["K"]], dtype=np.int64))
             else:
                 parts.append(np.array([l["kind"]], dtype=np.int64))
         return np.concatenate(parts)
@@ -513,6 +534,8 @@ class ModelBuilder:
                 cur = cur.reshape(c, h // 2, 2, w_ // 2, 2).max(axis=(2, 4)).reshape(-1)
             elif l["kind"] == L_FLATTEN:
                 pass
+            elif l["kind"] == L_LOGITS:
+                cur = logits_apply(l, cur)
         return cur
 
 
@@ -596,6 +619,10 @@ class GraphBuilder:
     def gelu(self, src, in_scale=1.0 / 128.0):
         return self._add(dict(kind=L_GELU, multiplier=gelu_multiplier(in_scale)), [src])
 
+    def logits(self, src, rows, k):
+        """Logits::Argmax over a padded [rows][k] tensor (layers/transformer/logits.rs); its output must be the model's only output tensor"""
+        return self._add(dict(kind=L_LOGITS, rows=rows, K=k), [src])
+
     def set_outputs(self, edges):
         self.outputs = [tuple(e) for e in edges]
         return self
@@ -637,6 +664,8 @@ class GraphBuilder:
                 parts.append(np.array(pre, dtype=np.int64))
             elif k == L_GELU:
                 parts.append(np.array(pre + [l["multiplier"]], dtype=np.int64))
+            elif k == L_LOGITS:
+                parts.append(np.array(pre + [l["rows"], l["K"]], dtype=np.int64))
             else:
                 raise ValueError("GraphBuilder: unsupported node kind")
         return np.concatenate(parts)
@@ -688,6 +717,8 @@ class GraphBuilder:
                 y = layernorm_apply(l, a)[0]
             elif k == L_SOFTMAX:
                 y = softmax_apply(l, a)
+            elif k == L_LOGITS:
+                y = logits_apply(l, a)
             elif k == L_MHA:
                 S, H, D = l["shape"]
                 qh, kh, vh = (get(e).reshape(S, H, D).transpose(1, 0, 2) for e in edges)  # [h][s][d]
@@ -876,6 +907,40 @@ def token_mlp(seq, vocab, width, config, output_features=3, max_positions=0):
         mb.add_const(1, 1)
     mb.matmul(width).relu()
     mb.matmul(output_features, bias=False).relu()
+    return mb
+
+
+def logits_only(rows, k, config):
+    """one Logits::Argmax over a [rows][k] tensor (layers/transformer/logits.rs); rows and k powers of two. A row may spread over at most 255
+    (max - x is a row of the range table): inputs come from a Requant in a real model"""
+    assert rows == next_pow2(rows) and k == next_pow2(k)
+    return ModelBuilder((rows, k), config).logits()
+
+
+def lm_head(seq, k, vocab, config):
+    """the head of a language model: hidden states [seq][k] -> MatMul with the constant [k][vocab] matrix -> Requant -> Logits::Argmax: one token per position"""
+    mb = ModelBuilder((seq, k), config)
+    mb.matmul(vocab, bias=False).logits()
+    return mb
+
+
+def token_lm(seq, vocab, width, config, gelu=True, max_positions=0):
+    """next-token prediction end to end: tokens -> Embeddings -> + positional table -> Linear -> Requant -> GELU (or ReLU) -> lm head -> Requant ->
+    Logits::Argmax (layers/transformer/{embeddings,positional,logits}.rs, layers/matrix_mul.rs, layers/activation.rs). `vocab` is a power of two here:
+    a padded vocabulary would need its padding columns kept from winning the argmax."""
+    assert vocab == next_pow2(vocab)
+    mb = ModelBuilder((seq,), config)
+    mb.embeddings(vocab, width)
+    if max_positions:
+        mb.positional(max_positions)
+    else:
+        mb.add_const(1, 1)
+    mb.matmul(width)
+    if gelu:
+        mb.gelu()
+    else:
+        mb.relu()
+    mb.matmul(vocab, bias=False).logits()
     return mb
 
 

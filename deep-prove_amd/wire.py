@@ -30,6 +30,7 @@ L_DENSE, L_REQUANT, L_RELU, L_CONV, L_MAXPOOL, L_MATMUL, L_ADD, L_EMBED, L_POSIT
 # nodes of a model graph: MatMul / Add of two inputs share the reference's MatMulProof / AddProof variants with the constant forms (on the way
 # back from the wire format they come out as kinds 6 / 7); ConcatMatMul and QKV have their own
 L_MATMUL2, L_ADD2, L_CONCAT_MATMUL, L_QKV, L_LAYERNORM, L_SOFTMAX, L_MHA = 10, 11, 12, 13, 14, 15, 16
+L_LOGITS = 18  # Logits::Argmax: LogitsProof (layers/transformer/logits.rs:62-76)
 L_GELU = 17  # Activation::Gelu: the reference's ActivationProof, as for a Relu (back from the wire format it is kind 2)
 
 
@@ -137,6 +138,8 @@ def parse_stream(words):
                   "clearing_proof": {"sumcheck": r.iop(), "individual_claim": r.ve()}}
         elif kind == L_MAXPOOL:
             lp = {"sumcheck": r.iop(), "lookup": r.logup(), "zerocheck_evals": r.ve(), "variable_gap": r.u(), "commitments": [r.comm() for _ in range(r.u())]}
+        elif kind == L_LOGITS:
+            lp = {"logup_proof": r.logup(), "max_eval": r.e(), "max_commitment": r.comm(), "sumcheck_proof": r.iop(), "max_mat_eval": r.e(), "hadamard_proof": r.iop(), "input_eval": r.e()}
         else:
             raise ValueError(f"unknown layer kind {kind}")
         steps.append((node, kind, lp))
@@ -278,6 +281,10 @@ def to_serde_model(tree, conv=Conventions):
                 else:
                     body[k] = {"sumcheck": _iop(lp[k]["sumcheck"], c), "individual_claim": _ve(lp[k]["individual_claim"], c)}
             v = {"Convolution": body}
+        elif kind == L_LOGITS:  # LogitsProof (layers/transformer/logits.rs:62-76), fields in declaration order
+            v = {"Logits": {"logup_proof": _logup(lp["logup_proof"], c), "max_eval": _e(lp["max_eval"], c), "max_commitment": _comm(lp["max_commitment"], c),
+                            "sumcheck_proof": _iop(lp["sumcheck_proof"], c), "max_mat_eval": _e(lp["max_mat_eval"], c), "hadamard_proof": _iop(lp["hadamard_proof"], c),
+                            "input_eval": _e(lp["input_eval"], c)}}
         else:
             v = {"Pooling": {"sumcheck": _iop(lp["sumcheck"], c), "lookup": _logup(lp["lookup"], c), "zerocheck_evals": _ve(lp["zerocheck_evals"], c),
                              "variable_gap": lp["variable_gap"], "commitments": [_comm(k, c) for k in lp["commitments"]]}}
@@ -490,7 +497,7 @@ def from_rmp(data, conv=Conventions):
     w = _Writer(conv)
     w.w.append(MAGIC); w.w.append(len(model["steps"]))
     kinds = {"Dense": L_DENSE, "Requant": L_REQUANT, "Activation": L_RELU, "Convolution": L_CONV, "Pooling": L_MAXPOOL, "MatMul": L_MATMUL, "Add": L_ADD, "Embeddings": L_EMBED, "Positional": L_POSITIONAL,
-             "ConcatMatMul": L_CONCAT_MATMUL, "QKV": L_QKV, "LayerNorm": L_LAYERNORM, "Softmax": L_SOFTMAX, "Mha": L_MHA}
+             "ConcatMatMul": L_CONCAT_MATMUL, "QKV": L_QKV, "LayerNorm": L_LAYERNORM, "Softmax": L_SOFTMAX, "Mha": L_MHA, "Logits": L_LOGITS}
     for node in sorted(model["steps"]):
         (name, lp), = model["steps"][node].items()
         w.w.append(node); w.w.append(kinds[name])
@@ -550,6 +557,8 @@ def from_rmp(data, conv=Conventions):
             w.w.append(len(lp["commits"]))
             for k in lp["commits"]:
                 w.comm(k)
+        elif name == "Logits":
+            w.logup(lp["logup_proof"]); w.e(lp["max_eval"]); w.comm(lp["max_commitment"]); w.iop(lp["sumcheck_proof"]); w.e(lp["max_mat_eval"]); w.iop(lp["hadamard_proof"]); w.e(lp["input_eval"])
         elif name == "Convolution":
             w.iop(lp["fft_proof"]); w.iop(lp["fft_proof_weights"])
             for k in ("fft_delegation_proof", "fft_delegation_proof_weights"):

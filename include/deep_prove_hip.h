@@ -346,8 +346,15 @@ int32_t dp_pcs_simple_batch_verify(size_t max_poly_size, const uint64_t root[4],
  *      rows of its table (its output column, round(127 gelu(i / 2^12)) in f32 with the C library's tanhf, is a commitment of the context). Proved as the
  *      reference's ActivationProof; the committed scaled-input column is opened at the lookup's own claim — what verify_activation checks (:495-505); the
  *      reference's prover files that claim divided by the multiplier (:405-430) and only verifies where the column is opened by showing it (<= 2^7 entries).
- *   A node has one, two or (kind 16) three inputs. Embeddings stay the first node of a chain. Not built: Logits (no consistent transcript in the
- *   reference outside cfg(test)). */
+ *   18 Logits (zkml/src/layers/transformer/logits.rs, Logits::Argmax; also the last layer of a chain): rows, K (powers of two >= 2). The input is a
+ *      padded [rows][K] tensor, the output `rows` words: per row the index of the FIRST occurrence of its maximum (max_in_slice, zkml/src/lib.rs:194-206;
+ *      a row of equal values gives 0). The argmax runs over the PADDED row, as the reference's does (logits.rs:90-125 ignores the unpadded shapes): a
+ *      front end that pads a vocabulary must keep its padding columns from winning. Refused at setup (DP_ERR_ARG) unless its output is the model's ONLY
+ *      output tensor, read by no node, and its input has rows * K entries. Proving needs max - x within 0 .. 255 in every row (a row of the range table;
+ *      the input comes out of a Requant in practice) and refuses other data with DP_ERR_ARG; the plain inference calls answer on any data. The proof step is
+ *      the reference prover's LogitsProof; the verifier checks it against the tokens of the output it is given (a token outside 0 .. K - 1 is DP_ERR_VERIFY)
+ *      and draws the output-claim challenges the prover drew — the reference's own verifier draws none there outside cfg(test) and cannot accept the stream.
+ *   A node has one, two or (kind 16) three inputs. Embeddings stay the first node of a chain. */
 int32_t dp_model_setup(dp_ctx* ctx, const int64_t* model_blob, size_t nwords, dp_model** out);
 int32_t dp_model_free(dp_model* m);
 /* runs inference on the host (Model::run, not part of proving time) then Prover::prove on the device.

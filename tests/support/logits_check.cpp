@@ -1,0 +1,107 @@
+// TEST HARNESS (tests/ only): Logits::Argmax (layer kind 18) through the product's host logic over the CPU test double — model blob -> setup ->
+// inference -> proof stream -> the product verifier (through the serialised verifier context, as dp_verify gets it), flip sweeps and forgeries.
+// Files are raw little-endian words (int64 blob / input / output, u64 stream).
+// usage: logits_check run <blob> <input> [<stream out> <output out>]      prove, verify, parse -> serialise
+//        logits_check flips <blob> <input> all | step                      every word | every word of the Logits step + every third of the first 8000 others
+//        logits_check token <blob> <input> <row> <value>                   the true stream against io.output with one token replaced
+//        logits_check zero_input_eval <blob> <input>                       input_eval = 0: only the division of the output evaluation can trip
+//        logits_check selfcheck <blob> <input>                             the true stream accepted, a forged token and input_eval = 0 refused, in one process
+#include "cpu_dev.hpp"
+#include "../../deep-prove_amd/csrc/zkml.h"
+#include "../../deep-prove_amd/csrc/blob.h"
+#include <cstdio>
+#include <string>
+#include <thread>
+
+template <class T> static std::vector<T> read_words(const char* path) {
+  FILE* f = fopen(path, "rb"); if (!f) { fprintf(stderr, "cannot open %s\n", path); exit(3); }
+  std::vector<T> v; T x; while (fread(&x, sizeof x, 1, f) == 1) v.push_back(x); fclose(f); return v;
+}
+template <class T> static void write_words(const char* path, const std::vector<T>& v) {
+  FILE* f = fopen(path, "wb"); if (!f || fwrite(v.data(), sizeof(T), v.size(), f) != v.size()) { fprintf(stderr, "cannot write %s\n", path); exit(3); } fclose(f);
+}
+// 0 accepted, 1 refused by the verifier (DP_ERR_VERIFY), 2 refused as malformed (any other DpError); `why` gets the message
+static int check(const dp::VerifierContext& vc, const std::vector<uint64_t>& w, const dp::IO& io, std::string* why = nullptr) {
+  try { dp::Proof q = dp::deserialize_proof(w.data(), w.size()); dp::Transcript vt = dp::default_transcript(); dp::verify(vc, q, io, vt); return 0; }
+  catch (const dp::DpError& e) { if (why) *why = e.what(); return e.code == dp::DP_ERR_VERIFY ? 1 : 2; }
+}
+
+int main(int argc, char** argv) {
+  if (argc < 4) { fprintf(stderr, "usage: logits_check run|flips|token|zero_input_eval <blob> <input> ...\n"); return 3; }
+  const std::string mode = argv[1];
+  const std::vector<int64_t> blob = read_words<int64_t>(argv[2]), in = read_words<int64_t>(argv[3]);
+  dp::ModelSpec m;
+  try { m = dp::parse_model(blob.data(), blob.size()); dp::validate_model(m); } catch (const dp::DpError& e) { printf("blob refused (%d): %s\n", e.code, e.what()); return 4; }
+  size_t lid = m.layers.size();
+  for (size_t id = 0; id < m.layers.size(); id++) if (m.layers[id].kind == dp::L_LOGITS) lid = id;
+  if (lid == m.layers.size()) { printf("no logits node\n"); return 4; }
+  dp::CpuDev dev;
+  auto ctx = dp::context_generate(dev, m);
+  dp::Trace tr = dp::run_model(m, in);  // (the plain inference answers whatever the rows spread over)
+  dp::IO io; io.input = in; io.output = dp::model_output(m, tr);
+  printf("output:"); for (int64_t v : io.output) printf(" %lld", (long long)v); printf("\n");
+  dp::Proof pp;
+  try { dp::Transcript pt = dp::default_transcript(); pp = dp::prove(*ctx, tr, pt); }
+  catch (const dp::DpError& e) { printf("prove: REFUSED (%d): %s\n", e.code, e.what()); return 5; }
+  const std::vector<uint64_t> pw = dp::serialize_proof(pp);
+  const std::vector<uint64_t> vcw = dp::vctx_to_words(ctx->verifier_ctx());
+  const dp::VerifierContext vc = dp::vctx_from_words(vcw.data(), vcw.size());
+  // where the Logits step lies in the stream: [magic, #steps] [steps in ascending id] [the rest]
+  size_t step_lo, step_hi;
+  { dp::Proof e0; const size_t rest0 = dp::serialize_proof(e0).size() - 2;
+    dp::Proof before; for (auto& kv : pp.steps) if (kv.first < lid) before.steps[kv.first] = kv.second;
+    step_lo = dp::serialize_proof(before).size() - rest0;
+    before.steps[lid] = pp.steps.at(lid);
+    step_hi = dp::serialize_proof(before).size() - rest0; }
+  if (mode == "selfcheck") {  // one process (the sanitised build proves slowly): the true stream, a forged token and the zero divisor
+    dp::IO bad = io; bad.output.at(0) = (io.output.at(0) + 1) % (int64_t)m.layers[lid].ncols;
+    dp::Proof q = pp; q.steps.at(lid).logits.input_eval = dp::ex_zero();
+    const int a = check(vc, pw, io), b = check(vc, pw, bad), c = check(vc, dp::serialize_proof(q), io);
+    printf("selfcheck: true stream %d, forged token %d, input_eval = 0 %d\n", a, b, c);
+    return a == 0 && b == 1 && c == 1 ? 0 : 1;
+  }
+  if (mode == "run") {
+    std::string why;
+    const int rc = check(vc, pw, io, &why);
+    printf("stream words=%zu logits step=[%zu, %zu)\n", pw.size(), step_lo, step_hi);
+    printf("verify(product): %s%s\n", rc == 0 ? "ACCEPT" : "REJECT: ", why.c_str());
+    dp::Proof q = dp::deserialize_proof(pw.data(), pw.size());
+    const bool rt = dp::serialize_proof(q) == pw;
+    printf("stream roundtrip: %s\n", rt ? "identity" : "FAILED");
+    if (argc >= 6) { write_words(argv[4], pw); write_words(argv[5], io.output); }
+    return rc == 0 && rt ? 0 : 1;
+  }
+  if (mode == "flips") {
+    const bool all = argc >= 5 && std::string(argv[4]) == "all";
+    size_t n_rest = 0; std::vector<size_t> ats;
+    for (size_t at = 0; at < pw.size(); at++) {
+      const bool in_step = at >= step_lo && at < step_hi;
+      if (!all && !in_step) { const size_t k = n_rest++; if (k >= 8000 || k % 3) continue; }
+      ats.push_back(at);
+    }
+    // every flip goes through the whole verifier; the verdicts are independent, so they are spread over a few host threads
+    const size_t nth = std::max<size_t>(1, std::min<size_t>(16, std::thread::hardware_concurrency()));
+    std::vector<char> ok(ats.size(), 0);
+    std::vector<std::thread> th;
+    for (size_t t = 0; t < nth; t++) th.emplace_back([&, t] { for (size_t i = t; i < ats.size(); i += nth) { std::vector<uint64_t> w = pw; w[ats[i]] ^= 1; ok[i] = check(vc, w, io) != 0; } });
+    for (std::thread& x : th) x.join();
+    size_t flipped = ats.size(), refused = 0; std::string accepted;
+    for (size_t i = 0; i < ats.size(); i++) { if (ok[i]) refused++; else accepted += " " + std::to_string(ats[i]); }
+    printf("flip sweep: %zu of %zu words flipped (logits step: %zu words), %zu refused, accepted at:%s\n", flipped, pw.size(), step_hi - step_lo, refused, accepted.c_str());
+    return flipped == refused && flipped >= step_hi - step_lo ? 0 : 1;
+  }
+  if (mode == "token" && argc >= 6) {
+    dp::IO bad = io; bad.output.at((size_t)atoll(argv[4])) = atoll(argv[5]);
+    std::string why; const int rc = check(vc, pw, bad, &why);
+    printf("verify(forged token): %s%s\n", rc == 0 ? "ACCEPT" : rc == 1 ? "REJECT: " : "MALFORMED: ", why.c_str());
+    return rc == 1 ? 0 : 1;
+  }
+  if (mode == "zero_input_eval") {
+    dp::Proof q = pp; q.steps.at(lid).logits.input_eval = dp::ex_zero();  // (no message of the transcript depends on it: the two sumchecks still verify)
+    std::string why; const int rc = check(vc, dp::serialize_proof(q), io, &why);
+    printf("verify(input_eval = 0): %s%s\n", rc == 0 ? "ACCEPT" : rc == 1 ? "REJECT: " : "MALFORMED: ", why.c_str());
+    return rc == 1 ? 0 : 1;
+  }
+  fprintf(stderr, "unknown mode\n");
+  return 3;
+}
