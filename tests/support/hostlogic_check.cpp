@@ -668,13 +668,15 @@ int main(int argc, char** argv) {
     catch (const std::exception& e) { printf("verify(%s%s): REJECT: %s\n", which ? "product" : "oracle", (tamper && !which) ? ",tampered" : "", e.what()); if (!(tamper && !which)) rc = 1; }
   }
   // DP_FLIP_SWEEP=start:stop:step — one proof, many single-word flips of the oracle's stream, each through the full verifier
+  // DP_FLIP_SWEEP_WHY=1: one more line per flipped position with the reason of its refusal (to compare two builds of the verifier)
   if (const char* fs = getenv("DP_FLIP_SWEEP")) {
     size_t a = 0, b = 0, st = 1; sscanf(fs, "%zu:%zu:%zu", &a, &b, &st); if (!st) st = 1; if (b > ow.size()) b = ow.size();
+    const bool say_why = getenv("DP_FLIP_SWEEP_WHY") && atoi(getenv("DP_FLIP_SWEEP_WHY"));
     size_t flipped = 0, rejected = 0; std::string accepted;
     for (size_t at = a; at < b; at += st) {
       std::vector<uint64_t> w = ow; w[at] ^= 1; flipped++;
-      try { dp::Proof q = dp::deserialize_proof(w.data(), w.size()); dp::Transcript vt = dp::default_transcript(); dp::verify(vc, q, io, vt); accepted += " " + std::to_string(at); }
-      catch (const std::exception&) { rejected++; }
+      try { dp::Proof q = dp::deserialize_proof(w.data(), w.size()); dp::Transcript vt = dp::default_transcript(); dp::verify(vc, q, io, vt); accepted += " " + std::to_string(at); if (say_why) printf("flip %zu: ACCEPT\n", at); }
+      catch (const std::exception& e) { rejected++; const dp::DpError* de = dynamic_cast<const dp::DpError*>(&e); if (say_why) printf("flip %zu: [%d] %s\n", at, de ? de->code : 1, e.what()); }  // [1]: not a DpError
     }
     printf("flip sweep: %zu flipped, %zu rejected, accepted at:%s\n", flipped, rejected, accepted.c_str());
   }

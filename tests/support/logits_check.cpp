@@ -3,6 +3,7 @@
 // Files are raw little-endian words (int64 blob / input / output, u64 stream).
 // usage: logits_check run <blob> <input> [<stream out> <output out>]      prove, verify, parse -> serialise
 //        logits_check flips <blob> <input> all | step                      every word | every word of the Logits step + every third of the first 8000 others
+//                                                                          (DP_FLIP_SWEEP_WHY=1: one more line per flipped word with the reason of its refusal)
 //        logits_check token <blob> <input> <row> <value>                   the true stream against io.output with one token replaced
 //        logits_check zero_input_eval <blob> <input>                       input_eval = 0: only the division of the output evaluation can trip
 //        logits_check selfcheck <blob> <input>                             the true stream accepted, a forged token and input_eval = 0 refused, in one process
@@ -81,10 +82,13 @@ int main(int argc, char** argv) {
     }
     // every flip goes through the whole verifier; the verdicts are independent, so they are spread over a few host threads
     const size_t nth = std::max<size_t>(1, std::min<size_t>(16, std::thread::hardware_concurrency()));
+    const bool say_why = getenv("DP_FLIP_SWEEP_WHY") && atoi(getenv("DP_FLIP_SWEEP_WHY"));
     std::vector<char> ok(ats.size(), 0);
+    std::vector<std::string> whys(say_why ? ats.size() : 0);
     std::vector<std::thread> th;
-    for (size_t t = 0; t < nth; t++) th.emplace_back([&, t] { for (size_t i = t; i < ats.size(); i += nth) { std::vector<uint64_t> w = pw; w[ats[i]] ^= 1; ok[i] = check(vc, w, io) != 0; } });
+    for (size_t t = 0; t < nth; t++) th.emplace_back([&, t] { for (size_t i = t; i < ats.size(); i += nth) { std::vector<uint64_t> w = pw; w[ats[i]] ^= 1; const int rc = check(vc, w, io, say_why ? &whys[i] : nullptr); ok[i] = rc != 0; if (say_why) whys[i] = "[" + std::to_string(rc) + "] " + whys[i]; } });
     for (std::thread& x : th) x.join();
+    for (size_t i = 0; i < whys.size(); i++) printf("flip %zu: %s\n", ats[i], whys[i].c_str());
     size_t flipped = ats.size(), refused = 0; std::string accepted;
     for (size_t i = 0; i < ats.size(); i++) { if (ok[i]) refused++; else accepted += " " + std::to_string(ats[i]); }
     printf("flip sweep: %zu of %zu words flipped (logits step: %zu words), %zu refused, accepted at:%s\n", flipped, pw.size(), step_hi - step_lo, refused, accepted.c_str());
