@@ -576,6 +576,13 @@ class Context:
         from .infer import infer_checked
         return infer_checked(self, inputs_i64, all_kinds=all_kinds)
 
+    def infer_trace(self, inputs_i64, all_kinds=False, checked=False):
+        """dp_model_infer_trace: infer() (checked: infer_checked()) that also returns every node's tensors, gathered on the device: returns
+        (rows[n, row_words], view, outputs[n, nout], reasons[n] or None, wall_ms) with view = {(node, role): rows[:, offset : offset + len]} —
+        roles 0, 1, 2: the node's output slots; 16, 17: the products and the probabilities inside an Mha node (deep_prove_amd.trace_layout)"""
+        from .infer import infer_trace
+        return infer_trace(self, inputs_i64, all_kinds=all_kinds, checked=checked)
+
     def free(self):
         if self.h:
             _lib.load().dp_model_free(self.h)
@@ -590,6 +597,7 @@ class Prover:
     def __init__(self, ctx):
         self.ctx = ctx
         self.last_prove_ms = None
+        self.last_infer_ms = None  # the device inference of the last prove_batch(..., device_infer=True)
         self._nout = None
 
     def prove(self, input_i64):
@@ -604,9 +612,31 @@ class Prover:
         return _take(pw, pn.value), out[:no.value].copy()
 
 
-    def prove_batch(self, inputs_i64, concurrency):
-        """independent proofs with up to `concurrency` in flight on this GPU; returns ([proof_words], outputs[nproofs, nout], wall_ms)"""
+    def _prove_batch_ex(self, x, concurrency, reasons):
+        """dp_model_prove_batch_ex with DP_PROVE_DEVICE_INFER; returns (proofs — None where refused —, outputs, wall_ms)"""
+        from .infer import PROVE_DEVICE_INFER, _load
+        lib = _load()
+        nproofs, ninput = x.shape
+        pws = (u64p * nproofs)()
+        pns = (C.c_size_t * nproofs)()
+        cap = self.output_len()
+        outs = np.empty((nproofs, cap), dtype=np.int64)
+        no = C.c_size_t(0)
+        ms, ims = C.c_double(), C.c_double()
+        check(lib.dp_model_prove_batch_ex(self.ctx.h, x.ctypes.data_as(i64p), nproofs, ninput, concurrency, PROVE_DEVICE_INFER,
+                                          reasons.ctypes.data_as(C.POINTER(C.c_uint32)) if reasons is not None else None, pws, pns,
+                                          outs.ctypes.data_as(i64p), cap, C.byref(no), C.byref(ms), C.byref(ims)))
+        self.last_infer_ms = ims.value
+        proofs = [_take(pws[i], pns[i]) if pws[i] else None for i in range(nproofs)]
+        return proofs, outs[:, :no.value].copy(), ms.value
+
+    def prove_batch(self, inputs_i64, concurrency, device_infer=False):
+        """independent proofs with up to `concurrency` in flight on this GPU; returns ([proof_words], outputs[nproofs, nout], wall_ms).
+        device_infer (dp_model_prove_batch_ex, DP_PROVE_DEVICE_INFER): the inputs are inferred on the device, with taps, instead of one by one on
+        the host — the same proofs word for word; wall_ms then covers inference and proving, last_infer_ms the inference"""
         x = np.ascontiguousarray(inputs_i64, dtype=np.int64)
+        if device_infer:
+            return self._prove_batch_ex(x, concurrency, None)
         nproofs, ninput = x.shape
         lib = _lib.load()
         pws = (u64p * nproofs)()
@@ -620,11 +650,17 @@ class Prover:
         proofs = [_take(pws[i], pns[i]) for i in range(nproofs)]
         return proofs, outs[:, :no.value].copy(), ms.value
 
-    def prove_batch_screened(self, inputs_i64, concurrency):
+    def prove_batch_screened(self, inputs_i64, concurrency, device_infer=False):
         """prove_batch that survives inputs the inference refuses (prove_batch raises on the whole batch for one of them): the batch is screened on
         the device (Context.infer_checked, all kinds) and the rows with reason 0 go to prove_batch — which is not called when there are none.
-        Returns (proofs, outputs[n, nout], reasons[n], wall_ms of the proving); proofs[i] is None and outputs[i] zeros where reasons[i] != 0"""
+        Returns (proofs, outputs[n, nout], reasons[n], wall_ms of the proving); proofs[i] is None and outputs[i] zeros where reasons[i] != 0.
+        device_infer: ONE call (dp_model_prove_batch_ex with reasons) — the inference that screens the batch is the one the proofs are made from;
+        wall_ms then covers it too"""
         x = np.ascontiguousarray(inputs_i64, dtype=np.int64)
+        if device_infer:
+            reasons = np.zeros(x.shape[0], dtype=np.uint32)
+            proofs, outs, ms = self._prove_batch_ex(x, concurrency, reasons)
+            return proofs, outs, reasons, ms
         screened, reasons, _ = self.ctx.infer_checked(x, all_kinds=True)
         good = np.flatnonzero(reasons == 0)
         proofs, outs, ms = [None] * x.shape[0], np.zeros_like(screened), 0.0

@@ -1285,10 +1285,16 @@ int32_t dp_model_prove(dp_model* m, const int64_t* input, size_t ninput, uint64_
     }
   });
 }
-int32_t dp_model_prove_batch(dp_model* m, const int64_t* inputs, size_t nproofs, size_t ninput, int32_t concurrency,
+}  // extern "C"
+// The body of dp_model_prove_batch and dp_model_prove_batch_ex: `nproofs` proofs with up to `concurrency` in flight. Proof k is that of input
+// at(k) = index ? index[k] : k — its words, its output row and its trace live at that number. `src` gives the trace of an input (by its number);
+// null: run_model on the input, on the thread that proves it or a helper (dp_model_prove_batch). Throws DpError.
+using TraceSource = std::function<Trace(size_t)>;
+static void prove_batch_body(dp_model* m, const int64_t* inputs, size_t nproofs, size_t ninput, int32_t concurrency, const TraceSource* src, const size_t* index,
                              uint64_t** proof_words, size_t* proof_nwords, int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms) {
-  return guard([&] {
+  {
     DP_REQUIRE(m && inputs && proof_words && proof_nwords && nproofs > 0 && concurrency > 0 && concurrency <= 1024, DP_ERR_ARG, "bad arguments");
+    auto at = [index](size_t k) { return index ? index[k] : k; };
     size_t nw = std::min<size_t>((size_t)concurrency, nproofs);
     // worker 0 is the model's own context; the others get their own stream + arena on the same GPU and share the
     // (read-only) model commitments
@@ -1363,7 +1369,7 @@ int32_t dp_model_prove_batch(dp_model* m, const int64_t* inputs, size_t nproofs,
     std::atomic<size_t> next(0);
     const bool timing = getenv("DP_TIMING") && atoi(getenv("DP_TIMING"));
     std::mutex err_mu; std::string err; int err_code = 0;
-    for (size_t i = 0; i < nproofs; i++) { proof_words[i] = nullptr; proof_nwords[i] = 0; }
+    for (size_t i = 0; i < nproofs; i++) { proof_words[at(i)] = nullptr; proof_nwords[at(i)] = 0; }
     for (size_t wi = 0; wi < nw && nco; wi++) hip_dev_cohort_attach(&dev_of(wi), m->cohorts[wi % nco]);
     // The host work a proof starts with — inference and the host half of the witness generation (zkml.h witness_host: lookup columns, table multiplicities;
     // 0.6 ms for Dense-4M, ~10 ms for the transformer layer) — is made AHEAD of the proofs by DP_PREP_THREADS helper threads (default 2, 0 = off): the members of
@@ -1375,7 +1381,7 @@ int32_t dp_model_prove_batch(dp_model* m, const int64_t* inputs, size_t nproofs,
     for (size_t i = 0; i < nproofs; i++) pst[i].store(0, std::memory_order_relaxed);
     auto make_prep = [&](size_t i) {
       std::unique_ptr<Prep> p(new Prep);
-      p->tr = run_model(m->zk->model, std::vector<int64_t>(inputs + i * ninput, inputs + (i + 1) * ninput));
+      p->tr = src ? (*src)(at(i)) : run_model(m->zk->model, std::vector<int64_t>(inputs + at(i) * ninput, inputs + (at(i) + 1) * ninput));
       p->wh = witness_host(*m->zk, p->tr);
       return p;
     };
@@ -1413,7 +1419,7 @@ int32_t dp_model_prove_batch(dp_model* m, const int64_t* inputs, size_t nproofs,
           if (ser_q.empty()) return;
           job = std::move(ser_q.front()); ser_q.pop_front();
         }
-        try { std::vector<u64> w = serialize_proof(job.second); proof_words[job.first] = copy_out(w); proof_nwords[job.first] = w.size(); }
+        try { std::vector<u64> w = serialize_proof(job.second); proof_words[at(job.first)] = copy_out(w); proof_nwords[at(job.first)] = w.size(); }
         catch (const std::exception& e) { std::lock_guard<std::mutex> g(err_mu); if (!err_code) { err_code = DP_ERR_OOM; err = std::string("serialising a proof: ") + e.what(); } }
       }
     };
@@ -1441,13 +1447,13 @@ int32_t dp_model_prove_batch(dp_model* m, const int64_t* inputs, size_t nproofs,
           if (nser) {  // several proofs in flight: the finished proof goes to the serialiser threads, this fiber to its next proof (see `ser_thread`)
             { std::lock_guard<std::mutex> g(ser_mu); ser_q.emplace_back(i, std::move(p)); }
             ser_cv.notify_one();
-          } else { static thread_local std::vector<u64> ser_buf; serialize_proof_to(p, ser_buf); proof_words[i] = copy_out(ser_buf); proof_nwords[i] = ser_buf.size(); }
+          } else { static thread_local std::vector<u64> ser_buf; serialize_proof_to(p, ser_buf); proof_words[at(i)] = copy_out(ser_buf); proof_nwords[at(i)] = ser_buf.size(); }
           auto h3 = std::chrono::steady_clock::now();
           if (timing && wi == 0) {
             auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
             fprintf(stderr, "[dp timing] host phases of one proof: inference + witness columns (or the wait for the helper that made them) %.2f ms, prove %.2f ms (wall, shared thread), serialise %.2f ms, copy out %.2f ms\n", ms(h0, h1), ms(h1, h2), ms(h2, h3), ms(h3, std::chrono::steady_clock::now()));
           }
-          if (outputs) { const std::vector<int64_t> o = model_output(m->zk->model, tr); DP_REQUIRE(o.size() <= noutput_cap, DP_ERR_ARG, "output buffer too small"); memcpy(outputs + i * noutput_cap, o.data(), o.size() * 8); if (noutput) *noutput = o.size(); }
+          if (outputs) { const std::vector<int64_t> o = model_output(m->zk->model, tr); DP_REQUIRE(o.size() <= noutput_cap, DP_ERR_ARG, "output buffer too small"); memcpy(outputs + at(i) * noutput_cap, o.data(), o.size() * 8); if (noutput) *noutput = o.size(); }
         }
       } catch (const DpError& e) { std::lock_guard<std::mutex> g(err_mu); if (!err_code) { err_code = e.code; err = e.what(); } next = nproofs; }
       catch (const std::exception& e) { std::lock_guard<std::mutex> g(err_mu); if (!err_code) { err_code = DP_ERR_ARG; err = e.what(); } next = nproofs; }
@@ -1509,7 +1515,68 @@ int32_t dp_model_prove_batch(dp_model* m, const int64_t* inputs, size_t nproofs,
     hip_dev_dump_sc_debug(m->ctx->dev); hip_dev_dump_host_stats(m->ctx->dev); hip_dump_wg_times();
     for (size_t wi = 1; wi < nw && wi < 3; wi++) { hip_dev_dump_sc_debug(m->workers[wi - 1].get()); hip_dev_dump_host_stats(m->workers[wi - 1].get()); }
     hip_dev_set_latency_mode(m->ctx->dev, true);
-    if (err_code) { for (size_t i = 0; i < nproofs; i++) { dp_free(proof_words[i]); proof_words[i] = nullptr; } throw DpError(err_code, err); }
+    if (err_code) { for (size_t i = 0; i < nproofs; i++) { dp_free(proof_words[at(i)]); proof_words[at(i)] = nullptr; proof_nwords[at(i)] = 0; } throw DpError(err_code, err); }
+  }
+}
+static void model_infer_run(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, double* wall_ms,
+                            int64_t* rows, size_t row_cap, size_t* row_words);
+extern "C" {
+int32_t dp_model_prove_batch(dp_model* m, const int64_t* inputs, size_t nproofs, size_t ninput, int32_t concurrency,
+                             uint64_t** proof_words, size_t* proof_nwords, int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms) {
+  return guard([&] { prove_batch_body(m, inputs, nproofs, ninput, concurrency, nullptr, nullptr, proof_words, proof_nwords, outputs, noutput_cap, noutput, wall_ms); });
+}
+// DP_PROVE_DEVICE_INFER: segment by segment, the device inference with taps on the model's own context — nothing of the model is in flight then:
+// the cohorts of the segment before have drained — and then prove_batch_body, whose trace source rebuilds the Trace of an input from its row
+// (trace_from_row; witness_host follows as ever). Workers and cohorts live on the model and persist between segments; what a segment costs
+// beyond its proofs is the ramp and the drain of the proofs in flight, once each, and an inference during which the prover is idle.
+int32_t dp_model_prove_batch_ex(dp_model* m, const int64_t* inputs, size_t nproofs, size_t ninput, int32_t concurrency, uint32_t flags, uint32_t* reasons,
+                                uint64_t** proof_words, size_t* proof_nwords, int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms, double* infer_ms) {
+  return guard([&] {
+    DP_REQUIRE(!(flags & ~(uint32_t)DP_PROVE_DEVICE_INFER), DP_ERR_ARG, "dp_model_prove_batch_ex: unknown flag bits");
+    DP_REQUIRE(!reasons || (flags & DP_PROVE_DEVICE_INFER), DP_ERR_ARG, "dp_model_prove_batch_ex: reasons need DP_PROVE_DEVICE_INFER");
+    if (infer_ms) *infer_ms = 0;
+    if (!flags) { prove_batch_body(m, inputs, nproofs, ninput, concurrency, nullptr, nullptr, proof_words, proof_nwords, outputs, noutput_cap, noutput, wall_ms); return; }
+    DP_REQUIRE(m && inputs && proof_words && proof_nwords && nproofs > 0 && concurrency > 0 && concurrency <= 1024, DP_ERR_ARG, "bad arguments");
+    const ModelSpec& spec = m->zk->model;
+    DP_REQUIRE(ninput == spec.input_len, DP_ERR_SHAPE, "input length mismatch");
+    const TraceLayout lay = trace_layout(spec);
+    const size_t nout = model_output_len(spec), rw = std::max<size_t>(lay.row_words, 1);
+    DP_REQUIRE(!outputs || noutput_cap >= nout, DP_ERR_ARG, "output buffer too small");
+    const char* mbs = getenv("DP_PROVE_TRACE_MB");
+    const size_t budget = (size_t)((mbs && atof(mbs) > 0 ? std::min(atof(mbs), 1.0e9) : 4096.0) * 1048576.0);  // (a fraction of a megabyte is allowed)
+    const size_t seg = std::min(nproofs, std::max<size_t>((size_t)concurrency, budget / (rw * 8)));
+    const bool timing = getenv("DP_TIMING") && atoi(getenv("DP_TIMING"));
+    for (size_t i = 0; i < nproofs; i++) { proof_words[i] = nullptr; proof_nwords[i] = 0; }
+    const auto t0 = std::chrono::steady_clock::now();
+    std::unique_ptr<int64_t[]> rows(new int64_t[seg * rw]);  // (not zero-filled: the inference writes every row it hands on)
+    std::vector<int64_t> outs(seg * std::max<size_t>(nout, 1));
+    std::vector<size_t> good;
+    double prove_ms = 0, inf_ms = 0;
+    size_t nsegments = 0;
+    try {
+      for (size_t s0 = 0; s0 < nproofs; s0 += seg, nsegments++) {
+        const size_t n = std::min(seg, nproofs - s0);
+        size_t no = 0, got_rw = 0; double ms = 0;
+        model_infer_run(m, inputs + s0 * ninput, n, ninput, DP_INFER_ALL_KINDS, outs.data(), std::max<size_t>(nout, 1), &no, reasons ? reasons + s0 : nullptr, &ms, rows.get(), rw, &got_rw);
+        inf_ms += ms;
+        good.clear();
+        for (size_t i = 0; i < n; i++) {
+          if (!reasons || reasons[s0 + i] == DP_INFER_OK) good.push_back(s0 + i);
+          else if (outputs) memset(outputs + (s0 + i) * noutput_cap, 0, nout * 8);
+        }
+        if (noutput) *noutput = nout;
+        if (good.empty()) continue;
+        const TraceSource src = [&, s0](size_t i) { return trace_from_row(spec, lay, inputs + i * ninput, rows.get() + (i - s0) * rw); };
+        double pms = 0;
+        prove_batch_body(m, inputs, good.size(), ninput, concurrency, &src, good.data(), proof_words, proof_nwords, outputs, noutput_cap, noutput, &pms);
+        prove_ms += pms;
+      }
+    } catch (...) { for (size_t i = 0; i < nproofs; i++) { dp_free(proof_words[i]); proof_words[i] = nullptr; proof_nwords[i] = 0; } throw; }
+    const double total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (timing) fprintf(stderr, "[dp timing] prove_batch_ex: %zu proofs in %zu segments of <= %zu, rows of %zu words (%.1f MB per segment), device inference %.3f ms, proving %.3f ms, the call %.3f ms\n",
+                        nproofs, nsegments, seg, lay.row_words, (double)(seg * rw * 8) / 1048576.0, inf_ms, prove_ms, total_ms);
+    if (wall_ms) *wall_ms = total_ms;
+    if (infer_ms) *infer_ms = inf_ms;
   });
 }
 int32_t dp_model_infer_host(const int64_t* model_blob, size_t nwords, const int64_t* input, size_t ninput, int64_t* output, size_t* noutput) {
@@ -1530,8 +1597,11 @@ int32_t dp_model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, size_
 static_assert(DP_INFER_OK == INFER_OK && DP_INFER_BAD_REQUANT == INFER_BAD_REQUANT && DP_INFER_BAD_TOKEN == INFER_BAD_TOKEN && DP_INFER_BAD_GELU == INFER_BAD_GELU &&
               DP_INFER_BAD_LAYERNORM == INFER_BAD_LAYERNORM && DP_INFER_BAD_SOFTMAX == INFER_BAD_SOFTMAX && INFER_BAD_LAYERNORM_TABLE > DP_INFER_BAD_SOFTMAX && DP_INFER_ALL_KINDS == INFER_ALL_KINDS, "deep_prove_hip_infer.h and infer.h");
 // reasons null: dp_model_infer_ex. Not null: dp_model_infer_checked (the same program and device constants for the same flag word)
-static int32_t model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, size_t* nrefused, double* wall_ms) {
-  return guard([&] {
+// rows not null: dp_model_infer_trace (the trace row of every input beside its outputs; row_cap words per row, *row_words = the words of one)
+}  // extern "C"
+static void model_infer_run(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, double* wall_ms,
+                            int64_t* rows, size_t row_cap, size_t* row_words) {
+  {
     DP_REQUIRE(m && inputs && outputs && noutput, DP_ERR_ARG, "bad arguments");
     DP_REQUIRE(!(flags & ~(uint32_t)DP_INFER_ALL_KINDS), DP_ERR_ARG, "dp_model_infer_ex: unknown flag bits");
     const ModelSpec& spec = m->zk->model;
@@ -1542,11 +1612,54 @@ static int32_t model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, s
     DP_REQUIRE(noutput_cap >= prog->output_len, DP_ERR_ARG, "output buffer too small");
     *noutput = prog->output_len;
     if (wall_ms) *wall_ms = 0;
-    if (nrefused) *nrefused = 0;
+    if (rows) { DP_REQUIRE(row_words && row_cap >= prog->row_words, DP_ERR_ARG, "dp_model_infer_trace: row buffer too small"); *row_words = prog->row_words; }
     if (!ninputs) return;
     if (!m->infer_state[flags]) m->infer_state[flags] = hip_infer_state_new(m->ctx->device_id);
-    hip_infer_run(m->ctx->dev, *prog, m->infer_state[flags], inputs, ninputs, outputs, noutput_cap, wall_ms, reasons);
+    hip_infer_run(m->ctx->dev, *prog, m->infer_state[flags], inputs, ninputs, outputs, noutput_cap, wall_ms, reasons, rows, row_cap);
+  }
+}
+extern "C" {
+static int32_t model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, size_t* nrefused, double* wall_ms) {
+  return guard([&] {
+    if (nrefused) *nrefused = 0;
+    model_infer_run(m, inputs, ninputs, ninput, flags, outputs, noutput_cap, noutput, reasons, wall_ms, nullptr, 0, nullptr);
     if (nrefused) for (size_t i = 0; i < ninputs; i++) *nrefused += reasons[i] != DP_INFER_OK;
+  });
+}
+int32_t dp_model_infer_trace(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* rows, size_t row_cap, size_t* row_words,
+                             int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, double* wall_ms) {
+  return guard([&] {
+    DP_REQUIRE(rows && row_words, DP_ERR_ARG, "bad arguments");
+    model_infer_run(m, inputs, ninputs, ninput, flags, outputs, noutput_cap, noutput, reasons, wall_ms, rows, row_cap, row_words);
+  });
+}
+// the model of a blob as dp_model_infer_host prepares it
+static ModelSpec host_model(const int64_t* model_blob, size_t nwords) {
+  ModelSpec m = parse_model(model_blob, nwords);
+  validate_model(m);
+  for (auto& l : m.layers) { prepare_fast_inference(l); if (l.kind == L_CONV) l.wfft = conv_weight_fft(l); }
+  return m;
+}
+int32_t dp_model_trace_layout(const int64_t* model_blob, size_t nwords, uint64_t* entries, size_t cap_entries, size_t* nentries, size_t* row_words) {
+  return guard([&] {
+    DP_REQUIRE(model_blob && nentries && row_words && (entries || !cap_entries), DP_ERR_ARG, "bad arguments");
+    ModelSpec m = parse_model(model_blob, nwords);
+    validate_model(m);
+    const TraceLayout lay = trace_layout(m);
+    *nentries = lay.entries.size(); *row_words = lay.row_words;
+    if (!entries) return;
+    DP_REQUIRE(cap_entries >= lay.entries.size(), DP_ERR_ARG, "entry buffer too small");
+    for (size_t k = 0; k < lay.entries.size(); k++) { const TraceEntry& e = lay.entries[k]; entries[4 * k] = e.node; entries[4 * k + 1] = e.role; entries[4 * k + 2] = e.off; entries[4 * k + 3] = e.len; }
+  });
+}
+int32_t dp_model_infer_host_trace(const int64_t* model_blob, size_t nwords, const int64_t* input, size_t ninput, int64_t* row, size_t* row_words) {
+  return guard([&] {
+    DP_REQUIRE(model_blob && input && row && row_words, DP_ERR_ARG, "bad arguments");
+    const ModelSpec m = host_model(model_blob, nwords);
+    const Trace tr = run_model(m, std::vector<int64_t>(input, input + ninput));
+    const TraceLayout lay = trace_layout(m);
+    DP_REQUIRE(*row_words >= lay.row_words, DP_ERR_ARG, "row buffer too small");
+    trace_to_row(m, lay, tr, row); *row_words = lay.row_words;
   });
 }
 int32_t dp_model_infer_ex(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms) {

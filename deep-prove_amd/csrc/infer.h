@@ -13,8 +13,14 @@
 // shift step works sample by sample and never reads the rows of a sample that is already refused. The two kinds of call differ only in what
 // hip_infer_run does with the words: with `reasons` (dp_model_infer_checked) it refuses inputs one by one, without (dp_model_infer_ex) the
 // first chunk that holds a refused sample ends the call with the host's message for its class. Program and constants are the same for both.
+// Tap mode (dp_model_infer_trace; `rows` of hip_infer_run): the trace row of every input (trace_row.h) comes back with its outputs. The planner
+// records for every entry of trace_layout the tensor that holds it (InferProgram::taps); after the last op of a chunk ONE launch of
+// k_infer_tap_pack gathers them into a sample-major image [sample][row_words], which travels to the host in one copy beside the outputs.
 #pragma once
 #include "dev.h"
+#ifdef DP_INFER_PLANNER
+#include "trace_row.h"
+#endif
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
@@ -54,8 +60,10 @@ struct InferOp {
   // IO_SOFTMAX: C, R, K, zero chunks, zero vars (in1 = the shift buffer of the chunk, a tensor of C * R words per sample); IO_ARGMAX: rows, K
   size_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
+struct InferTap { int tensor = -1; size_t len = 0, off = 0; };  // words off .. off + len of a trace row are tensor `tensor`
 struct InferProgram {
   size_t input_len = 0, output_len = 0;
+  std::vector<InferTap> taps; size_t row_words = 0;  // one tap per entry of trace_layout(model), in its order
   std::vector<InferTensor> tensors;
   std::vector<int> inputs, outputs;  // tensor ids of the model's input / output tensors, in the order they are concatenated
   std::vector<InferConst> consts;
@@ -70,7 +78,10 @@ void hip_infer_state_free(InferDeviceState* s);
 // inputs: ninputs x p.input_len words; outputs: ninputs x out_stride words (the first p.output_len of each row are written). Throws DpError.
 // reasons (ninputs words) not null: checked mode — bad data refuses its input (reasons[i] = INFER_BAD_*, the output row zeros), not the call, and
 // every chunk is processed. Null: the first chunk with a refused sample ends the call (DP_ERR_ARG, the host's message), none of its rows is written.
-void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* inputs, size_t ninputs, int64_t* outputs, size_t out_stride, double* wall_ms, uint32_t* reasons = nullptr);
+// rows not null: tap mode — row i of `rows` (ninputs x row_stride words, the first p.row_words of each written) is the trace row of input i; zeros
+// for an input refused in checked mode.
+void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* inputs, size_t ninputs, int64_t* outputs, size_t out_stride, double* wall_ms, uint32_t* reasons = nullptr,
+                   int64_t* rows = nullptr, size_t row_stride = 0);
 
 #ifdef DP_INFER_PLANNER  // (capi.cpp, after zkml.h)
 inline const char* infer_kind_name(int k) {
@@ -116,6 +127,7 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
   auto new_const = [&](const int64_t* h, size_t n) { InferConst c; c.h64 = h; c.n = n; p.consts.push_back(std::move(c)); return (int)p.consts.size() - 1; };
   for (size_t n : input_tensor_lens(m)) p.inputs.push_back(new_tensor(n, IQ_IF_INPUTS));
   std::vector<std::vector<int>> slot(m.layers.size());  // tensor of (node, output slot)
+  std::map<size_t, std::pair<int, int>> mha_inner;      // Mha node -> (the products its Softmax reads, the probabilities)
   auto tensor_of = [&](const Edge& e) { return e.from < 0 ? p.inputs.at((size_t)e.slot) : slot.at((size_t)e.from).at((size_t)e.slot); };
   // the constant [K][N] matrix (b_is_nk: stored [N][K]) of a product, with its int8 copy [N][K] when every weight fits and K * 128 * 128 < 2^31
   auto weight_const = [&](const int64_t* h, size_t K, size_t N, bool b_is_nk) {
@@ -202,7 +214,9 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
       const size_t n = l.mha_shape[0] * l.mha_shape[1] * l.mha_shape[2];
       const int kt = tensor_of(e[1]), vt = tensor_of(e[2]);
       DP_REQUIRE(alen == n && p.tensors[(size_t)kt].len == n && p.tensors[(size_t)vt].len == n, DP_ERR_SHAPE, "mha: input shapes");
-      slot[id] = {cm_gemm(id, mha_final_spec(l), softmax(id, mha_softmax_spec(l), cm_gemm(id, mha_qk_spec(l), a, kt)), vt)};
+      const int qk = cm_gemm(id, mha_qk_spec(l), a, kt), pr = softmax(id, mha_softmax_spec(l), qk);
+      mha_inner[id] = {qk, pr};
+      slot[id] = {cm_gemm(id, mha_final_spec(l), pr, vt)};
       DP_REQUIRE(p.tensors[(size_t)slot[id][0]].len == lens[id], DP_ERR_SHAPE, "dp_model_infer: tensor length");
       continue;
     }
@@ -255,6 +269,16 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
     p.ops.push_back(o); slot[id] = {o.out};
   }
   for (const Edge& e : output_edges(m)) p.outputs.push_back(tensor_of(e));
+  // the taps: the tensor behind every entry of the trace row, in the layout's order (a Flatten node's entry is the tensor it passes on)
+  const TraceLayout lay = trace_layout(m);
+  for (const TraceEntry& e : lay.entries) {
+    const size_t id = (size_t)e.node;
+    InferTap t; t.len = (size_t)e.len; t.off = (size_t)e.off;
+    t.tensor = e.role == TRACE_ROLE_MHA_IN ? mha_inner.at(id).first : e.role == TRACE_ROLE_MHA_OUT ? mha_inner.at(id).second : slot.at(id).at((size_t)e.role);
+    DP_REQUIRE(p.tensors[(size_t)t.tensor].len == t.len, DP_ERR_SHAPE, "dp_model_infer: tap length");
+    p.taps.push_back(t);
+  }
+  p.row_words = lay.row_words;
   // (m is the model of the dp_model that keeps this program: it outlives it)
   p.shifts = [&m](const InferOp& o, const int64_t* x, size_t nb, int64_t* shifts, uint32_t* status) {
     const LayerSpec& l = m.layers[(size_t)o.node];

@@ -259,6 +259,24 @@ __global__ __launch_bounds__(256) void k_infer_store(const int64_t* __restrict__
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[(i / len) * stride + off + i % len] = x[i];
 }
+// Tap mode: the trace rows of the chunk. Tap blockIdx.y (uniform per workgroup: the descriptor is read once, in scalar registers) is tensor `src`,
+// [sample][len] words, and goes to words off .. off + len of every sample's row of the sample-major image [sample][row_words]. The workgroups of
+// a tap stride over its nb * len words: reads are consecutive throughout, writes consecutive within runs of len. A copy of 16 bytes per word
+// (8 read, 8 written), plain vector loads and stores; any len and off (odd ones, len below or no multiple of the wave). 32-bit index arithmetic
+// when the tap's words of the chunk can be counted in 31 bits. In bounds: j < nb * len (the tensor's words of the chunk), s < nb and
+// off + e < row_words (the planner's layout: off + len <= row_words)
+struct InferTapDesc { const int64_t* src; unsigned long long len, off; };
+__global__ __launch_bounds__(256) void k_infer_tap_pack(const InferTapDesc* __restrict__ taps, int64_t* __restrict__ img, size_t row_words, size_t nb) {
+  const InferTapDesc t = taps[blockIdx.y];
+  const size_t n = nb * t.len, step = (size_t)gridDim.x * blockDim.x, i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t* dst = img + t.off;
+  if (n <= 0x7fffffffu - step) {
+    const unsigned len = (unsigned)t.len, n32 = (unsigned)n, st32 = (unsigned)step;
+    for (unsigned j = (unsigned)i0; j < n32; j += st32) { const unsigned s = j / len, e = j - s * len; dst[(size_t)s * row_words + e] = t.src[j]; }
+  } else {
+    for (size_t j = i0; j < n; j += step) { const size_t s = j / t.len, e = j - s * t.len; dst[s * row_words + e] = t.src[j]; }
+  }
+}
 
 struct InferDeviceState {
   int device = 0;
@@ -280,19 +298,21 @@ static const int8_t* infer_const8(const InferProgram& p, InferDeviceState* st, i
 
 // The scratch of one chunk (outside the arenas, released before the call returns): [tensors, int64 | int8][input block][output block][one status
 // word per sample]; and the pinned block of the host side: the input block on its way up, the output block with the status words behind it on
-// its way down and, at the shift step of a Softmax, [its input of the chunk][the status words][the shifts]
+// its way down and, at the shift step of a Softmax, [its input of the chunk][the status words][the shifts]. Tap mode alone appends [the tap
+// descriptors][the image of the chunk's trace rows] to the device block and the image's twin, behind the output block, to the pinned one
 struct InferScratch {
   bool in_q = true;     // model inputs within -128..127 (checked on the host, for the whole call): they travel as int8 and count as quantised tensors
   std::vector<char> q;  // tensor t has an int8 copy
   std::vector<size_t> off64, off8;
   size_t chunk = 1, off_in = 0, off_out = 0, off_stat = 0, total = 0, sm_in = 0, sm_stat = 0, pinned_bytes = 0;
+  size_t off_taps = 0, off_img = 0, pin_img = 0;  // (tap mode)
   char* dev = nullptr; char* pinned = nullptr;
   int64_t* T64(int t) const { return (int64_t*)(dev + off64[(size_t)t]); }
   int8_t* T8(int t) const { return q[(size_t)t] ? (int8_t*)(dev + off8[(size_t)t]) : (int8_t*)nullptr; }
   unsigned* status() const { return (unsigned*)(dev + off_stat); }
   uint32_t* sm_status() const { return (uint32_t*)(pinned + sm_in); }
 };
-static InferScratch infer_layout(const InferProgram& p, const int64_t* inputs, size_t ninputs) {
+static InferScratch infer_layout(const InferProgram& p, const int64_t* inputs, size_t ninputs, bool taps) {
   const char* mbs = getenv("DP_INFER_SCRATCH_MB");
   const size_t scratch_cap = (mbs && atoll(mbs) > 0 ? (size_t)atoll(mbs) : size_t(1024)) << 20, nt = p.tensors.size();
   InferScratch m;
@@ -302,6 +322,7 @@ static InferScratch infer_layout(const InferProgram& p, const int64_t* inputs, s
   auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
   for (size_t t = 0; t < nt; t++) { m.q[t] = p.tensors[t].q == IQ_YES || (p.tensors[t].q == IQ_IF_INPUTS && m.in_q); per_sample += p.tensors[t].len * (m.q[t] ? 9 : 8); }
   per_sample += p.input_len * (m.in_q ? 1 : 8) + p.output_len * 8;
+  if (taps) per_sample += p.row_words * 16;  // (the image and its pinned twin)
   const size_t chunk = m.chunk = std::max<size_t>(1, std::min(ninputs, scratch_cap / std::max<size_t>(per_sample, 1)));
   for (size_t t = 0; t < nt; t++) { m.off64[t] = m.total; m.total += up(chunk * p.tensors[t].len * 8); m.off8[t] = m.total; if (m.q[t]) m.total += up(chunk * p.tensors[t].len); }
   const size_t in_bytes = chunk * p.input_len * (m.in_q ? 1 : 8), out_bytes = chunk * p.output_len * 8 + chunk * 4;
@@ -311,6 +332,11 @@ static InferScratch infer_layout(const InferProgram& p, const int64_t* inputs, s
   for (const InferOp& o : p.ops) if (o.kind == IO_SOFTMAX) { m.sm_in = std::max(m.sm_in, up(chunk * p.tensors[(size_t)o.in0].len * 8)); sm_sh = std::max(sm_sh, chunk * p.tensors[(size_t)o.in1].len * 8); }
   m.sm_stat = up(chunk * 4);
   m.pinned_bytes = std::max(std::max(in_bytes, out_bytes), m.sm_in + m.sm_stat + sm_sh);
+  if (taps) {
+    m.off_taps = m.total; m.total += up(p.taps.size() * sizeof(InferTapDesc));
+    m.off_img = m.total; m.total += up(chunk * p.row_words * 8);
+    m.pin_img = up(out_bytes); m.pinned_bytes = std::max(std::max(m.pinned_bytes, m.pin_img + chunk * p.row_words * 8), p.taps.size() * sizeof(InferTapDesc));
+  }
   return m;
 }
 // The one table of what the host says of refused data: the message of a class (infer.h), and the order in which a plain call that met several
@@ -369,24 +395,41 @@ static void infer_shift_trip(const InferProgram& p, const InferOp& o, const Infe
   HIP_CHECK(hipMemcpyAsync(m.status(), m.sm_status(), nb * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(m.T64(o.in1), shifts, nsh * 8, hipMemcpyHostToDevice, s));
 }
-
-void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* inputs, size_t ninputs, int64_t* outputs, size_t out_stride, double* wall_ms, uint32_t* reasons) {
+void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* inputs, size_t ninputs, int64_t* outputs, size_t out_stride, double* wall_ms, uint32_t* reasons,
+                   int64_t* rows, size_t row_stride) {
   HipDev* hd = static_cast<HipDev*>(d);
   hd->bind_thread(); hd->sync();
   hipStream_t s = hd->stream();
   static const bool log_line = getenv("DP_INFER_LOG") && atoi(getenv("DP_INFER_LOG"));
   const auto t0 = std::chrono::steady_clock::now();
-  InferScratch m = infer_layout(p, inputs, ninputs);
+  const bool taps = rows != nullptr;
+  DP_REQUIRE(!taps || (row_stride >= p.row_words && p.taps.size() >= 1 && p.taps.size() <= 65535), DP_ERR_ARG, "dp_model_infer_trace: row buffer too small");
+  InferScratch m = infer_layout(p, inputs, ninputs, taps);
+  size_t tap_max = 0, tap_launches = 0;
+  for (const InferTap& t : p.taps) tap_max = std::max(tap_max, t.len);
+  hipEvent_t tap_ev[2] = {nullptr, nullptr};  // (DP_INFER_LOG in tap mode: the time of the chunks' k_infer_tap_pack launches)
+  double tap_ms = 0;
   const size_t chunk = m.chunk, in_w = m.in_q ? 1 : 8;
   st->c64.resize(p.consts.size(), nullptr); st->c8.resize(p.consts.size(), nullptr);
   size_t launches[IO_KINDS + 3] = {0}, nchunks = 0, trips = 0, nrefused = 0;
   double trip_ms = 0;
   uint32_t stop = INFER_OK;  // plain mode (no `reasons`): the class of the refused sample that ends the call
-  auto cleanup = [&] { (void)hipStreamSynchronize(s); if (m.dev) (void)hipFree(m.dev); if (m.pinned) (void)hipHostFree(m.pinned); m.dev = m.pinned = nullptr; };
+  auto cleanup = [&] {
+    (void)hipStreamSynchronize(s); if (m.dev) (void)hipFree(m.dev); if (m.pinned) (void)hipHostFree(m.pinned); m.dev = m.pinned = nullptr;
+    for (hipEvent_t& e : tap_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+  };
   try {
     HIP_CHECK(hipMalloc((void**)&m.dev, m.total));
     HIP_CHECK(hipHostMalloc((void**)&m.pinned, m.pinned_bytes, hipHostMallocDefault));
     int64_t* dout = (int64_t*)(m.dev + m.off_out);
+    if (taps) {  // the descriptors: made in the pinned block, uploaded once per call (the copy has landed before the block is written again)
+      InferTapDesc* h = (InferTapDesc*)m.pinned;
+      DP_REQUIRE(p.taps.size() * sizeof(InferTapDesc) <= m.pinned_bytes, DP_ERR_ARG, "dp_model_infer_trace: tap descriptors");
+      for (size_t k = 0; k < p.taps.size(); k++) h[k] = InferTapDesc{m.T64(p.taps[k].tensor), p.taps[k].len, p.taps[k].off};
+      HIP_CHECK(hipMemcpyAsync(m.dev + m.off_taps, h, p.taps.size() * sizeof(InferTapDesc), hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      if (log_line) for (hipEvent_t& e : tap_ev) HIP_CHECK(hipEventCreate(&e));
+    }
     for (size_t b0 = 0; b0 < ninputs && !stop; b0 += chunk) {
       const size_t nb = std::min(chunk, ninputs - b0), nin = nb * p.input_len, nout = nb * p.output_len;
       nchunks++;
@@ -416,18 +459,29 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
         k_infer_store<<<infer_grid(n), 256, 0, s>>>(m.T64(t), len, dout, p.output_len, ooff, n);
         ooff += len; launches[IO_KINDS + 1]++;
       }
+      if (taps) {
+        const unsigned gx = (unsigned)std::max<size_t>(1, std::min<size_t>((nb * tap_max + 255) / 256, 1024));
+        if (tap_ev[0]) HIP_CHECK(hipEventRecord(tap_ev[0], s));
+        k_infer_tap_pack<<<dim3(gx, (unsigned)p.taps.size()), 256, 0, s>>>((const InferTapDesc*)(m.dev + m.off_taps), (int64_t*)(m.dev + m.off_img), p.row_words, nb);
+        if (tap_ev[1]) HIP_CHECK(hipEventRecord(tap_ev[1], s));
+        tap_launches++;
+      }
       HIP_CHECK(hipGetLastError());
+      if (taps) HIP_CHECK(hipMemcpyAsync(m.pinned + m.pin_img, m.dev + m.off_img, nb * p.row_words * 8, hipMemcpyDeviceToHost, s));
       // the outputs and the status words behind them: one copy (a partial last chunk: the words are fetched on their own)
       if (nb == chunk) HIP_CHECK(hipMemcpyAsync(m.pinned, dout, nout * 8 + nb * 4, hipMemcpyDeviceToHost, s));
       else { HIP_CHECK(hipMemcpyAsync(m.pinned, dout, nout * 8, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipMemcpyAsync(m.pinned + nout * 8, m.status(), nb * 4, hipMemcpyDeviceToHost, s)); }
       HIP_CHECK(hipStreamSynchronize(s));
       const uint32_t* hs = (const uint32_t*)(m.pinned + nout * 8);
+      if (tap_ev[1]) { float ems = 0; HIP_CHECK(hipEventElapsedTime(&ems, tap_ev[0], tap_ev[1])); tap_ms += ems; }
       if (!reasons && (stop = infer_first_class(hs, nb))) break;  // (none of the chunk's rows is copied out)
       for (size_t i = 0; i < nb; i++) {  // refused samples (checked mode): the public reason, and zeros for whatever the later kernels made of them
         const uint32_t cls = hs[i] == INFER_BAD_LAYERNORM_TABLE ? INFER_BAD_LAYERNORM : hs[i];
         if (reasons) reasons[b0 + i] = cls;
         if (cls) { memset(outputs + (b0 + i) * out_stride, 0, p.output_len * 8); nrefused++; }
         else memcpy(outputs + (b0 + i) * out_stride, m.pinned + i * p.output_len * 8, p.output_len * 8);
+        if (taps && cls) memset(rows + (b0 + i) * row_stride, 0, p.row_words * 8);
+        else if (taps) memcpy(rows + (b0 + i) * row_stride, m.pinned + m.pin_img + i * p.row_words * 8, p.row_words * 8);
       }
     }
   } catch (...) { cleanup(); throw; }
@@ -435,8 +489,10 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (wall_ms) *wall_ms = ms;
   const size_t n_i8 = launches[IO_KINDS + 2], n_i64 = launches[IO_GEMM] + launches[IO_GEMM2] - n_i8;
-  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu conv %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu argmax %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s\n",
+  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu conv %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu argmax %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s%s\n",
                    n_i8, n_i64, launches[IO_CONV], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], launches[IO_ARGMAX], trips, trip_ms,
-                   ninputs, nchunks, chunk, (double)m.total / 1048576.0, m.in_q ? "int8" : "int64", ms, reasons ? ("; checked, refused " + std::to_string(nrefused)).c_str() : "");
+                   ninputs, nchunks, chunk, (double)m.total / 1048576.0, m.in_q ? "int8" : "int64", ms,
+                   taps ? ("; taps " + std::to_string(p.taps.size()) + " entries, " + std::to_string(p.row_words) + " words, pack_launches " + std::to_string(tap_launches) + " pack_ms " + std::to_string(tap_ms)).c_str() : "",
+                   reasons ? ("; checked, refused " + std::to_string(nrefused)).c_str() : "");
   DP_REQUIRE(!stop, DP_ERR_ARG, INFER_REFUSAL[stop]);
 }

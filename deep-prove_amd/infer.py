@@ -1,4 +1,5 @@
-"""Batched quantised inference on the device: ctypes binding of include/deep_prove_hip_infer.h (dp_model_infer, dp_model_infer_ex, dp_model_infer_checked). The entry points have a header and a
+"""Batched quantised inference on the device: ctypes binding of include/deep_prove_hip_infer.h (dp_model_infer, dp_model_infer_ex, dp_model_infer_checked; the trace row: dp_model_trace_layout, dp_model_infer_host_trace, dp_model_infer_trace;
+dp_model_prove_batch_ex is bound here and called by api.Prover). The entry points have a header and a
 binding table of its own: `_lib.SIGNATURES` lists exactly the symbols of include/deep_prove_hip.h."""
 import ctypes as C
 import os
@@ -13,8 +14,16 @@ INFER_SIGNATURES = {
     "dp_model_infer": (C.c_int32, [vp, i64p, C.c_size_t, C.c_size_t, i64p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_double)]),
     "dp_model_infer_ex": (C.c_int32, [vp, i64p, C.c_size_t, C.c_size_t, C.c_uint32, i64p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_double)]),
     "dp_model_infer_checked": (C.c_int32, [vp, i64p, C.c_size_t, C.c_size_t, C.c_uint32, i64p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.POINTER(C.c_double)]),
+    "dp_model_trace_layout": (C.c_int32, [i64p, C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "dp_model_infer_host_trace": (C.c_int32, [i64p, C.c_size_t, i64p, C.c_size_t, i64p, C.POINTER(C.c_size_t)]),
+    "dp_model_infer_trace": (C.c_int32, [vp, i64p, C.c_size_t, C.c_size_t, C.c_uint32, i64p, C.c_size_t, C.POINTER(C.c_size_t), i64p, C.c_size_t, C.POINTER(C.c_size_t),
+                                         C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
+    "dp_model_prove_batch_ex": (C.c_int32, [vp, i64p, C.c_size_t, C.c_size_t, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_size_t),
+                                            i64p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 ALL_KINDS = 1  # DP_INFER_ALL_KINDS
+PROVE_DEVICE_INFER = 1  # DP_PROVE_DEVICE_INFER
+ROLE_MHA_IN, ROLE_MHA_OUT = 16, 17  # DP_TRACE_ROLE_MHA_IN / _OUT: the two inner tensors of an Mha node in a trace row
 # DP_INFER_OK, DP_INFER_BAD_*: the status of one input of dp_model_infer_checked
 REASONS = {0: "ok", 1: "requant", 2: "token", 3: "gelu", 4: "layernorm", 5: "softmax"}
 
@@ -72,3 +81,50 @@ def infer_checked(ctx, inputs_i64, all_kinds=False, flags=None):
                                      reasons.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(nref), C.byref(ms)))
     assert nref.value == int(np.count_nonzero(reasons))
     return outs[:, :no.value].copy(), reasons, ms.value
+
+
+def trace_layout(model_blob):
+    """dp_model_trace_layout: (entries, row_words) of a model blob — entries = [(node, role, offset, len)] in the order of a trace row: per node
+    the two inner tensors of an Mha node (roles 16, 17), then its output slots (roles 0, 1, 2). Host only."""
+    lib = _load()
+    b = np.ascontiguousarray(model_blob, dtype=np.int64)
+    ne, rw = C.c_size_t(0), C.c_size_t(0)
+    check(lib.dp_model_trace_layout(b.ctypes.data_as(i64p), b.size, None, 0, C.byref(ne), C.byref(rw)))
+    ent = np.zeros((ne.value, 4), dtype=np.uint64)
+    check(lib.dp_model_trace_layout(b.ctypes.data_as(i64p), b.size, ent.ctypes.data_as(C.POINTER(C.c_uint64)), ne.value, C.byref(ne), C.byref(rw)))
+    return [tuple(int(v) for v in e) for e in ent], int(rw.value)
+
+
+def trace_view(entries, rows):
+    """{(node, role): rows[..., offset : offset + len]} — views into a trace row, or into the rows of a batch"""
+    return {(node, role): rows[..., off:off + n] for node, role, off, n in entries}
+
+
+def infer_host_trace(model_blob, input_i64):
+    """dp_model_infer_host_trace: the trace row of one input on the host (run_model, flattened by trace_layout); the errors of infer_host"""
+    lib = _load()
+    b = np.ascontiguousarray(model_blob, dtype=np.int64)
+    x = np.ascontiguousarray(input_i64, dtype=np.int64)
+    ne, rw = C.c_size_t(0), C.c_size_t(0)
+    check(lib.dp_model_trace_layout(b.ctypes.data_as(i64p), b.size, None, 0, C.byref(ne), C.byref(rw)))
+    row = np.empty(max(rw.value, 1), dtype=np.int64)
+    n = C.c_size_t(row.size)
+    check(lib.dp_model_infer_host_trace(b.ctypes.data_as(i64p), b.size, x.ctypes.data_as(i64p), x.size, row.ctypes.data_as(i64p), C.byref(n)))
+    return row[:n.value].copy()
+
+
+def infer_trace(ctx, inputs_i64, all_kinds=False, checked=False, flags=None):
+    """dp_model_infer_trace: infer() (or, checked, infer_checked()) that also returns the trace row of every input, gathered on the device. Returns
+    (rows[n, row_words], view, outputs[n, nout], reasons[n] or None, wall_ms); view = {(node, role): rows[:, offset : offset + len]}. Row i holds
+    the integers of infer_host_trace for input i; checked: zeros where reasons[i] != 0."""
+    lib, x, outs, flags = _prepare(ctx, inputs_i64, all_kinds, flags)
+    entries, rw = trace_layout(ctx.model_blob)
+    rows = np.empty((x.shape[0], max(rw, 1)), dtype=np.int64)
+    reasons = np.zeros(x.shape[0], dtype=np.uint32) if checked else None
+    no, got = C.c_size_t(0), C.c_size_t(0)
+    ms = C.c_double()
+    check(lib.dp_model_infer_trace(ctx.h, x.ctypes.data_as(i64p), x.shape[0], x.shape[1], flags, rows.ctypes.data_as(i64p), rows.shape[1], C.byref(got),
+                                   outs.ctypes.data_as(i64p), outs.shape[1], C.byref(no), reasons.ctypes.data_as(C.POINTER(C.c_uint32)) if checked else None, C.byref(ms)))
+    assert got.value == rw
+    rows = rows[:, :rw].copy()
+    return rows, trace_view(entries, rows), outs[:, :no.value].copy(), reasons, ms.value

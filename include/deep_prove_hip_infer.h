@@ -37,7 +37,7 @@
  * Knobs (environment): DP_INFER_SCRATCH_MB (activation scratch of one chunk of the batch, default 1024), DP_INFER_NO_MFMA=1 (64-bit
  * products everywhere), DP_INFER_LOG=1 (one `[dp infer]` line per call on stderr: launches per kernel, chunks, wall time; gelu / layernorm / softmax launches,
  * shift_trips = round trips of the Softmax shift step and shift_ms = the milliseconds spent in them; a checked call appends
- * `; checked, refused N`).
+ * `; checked, refused N`), DP_PROVE_TRACE_MB (host memory for the trace rows of one segment of dp_model_prove_batch_ex, default 4096).
  */
 #ifndef DEEP_PROVE_HIP_INFER_H
 #define DEEP_PROVE_HIP_INFER_H
@@ -70,6 +70,50 @@ int32_t dp_model_infer_ex(dp_model* m, const int64_t* inputs, size_t ninputs, si
 int32_t dp_model_infer_checked(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags,
                                int64_t* outputs, size_t noutput_cap, size_t* noutput,
                                uint32_t* reasons /* ninputs */, size_t* nrefused /* nullable */, double* wall_ms /* nullable */);
+
+/* ---- The trace row: every tensor the prover reads of one inference, as one row of int64 words.
+ * A row is described by entries (node, role, offset, len), in node order. Within a node: for an Mha node role DP_TRACE_ROLE_MHA_IN (the products
+ * Q K^T its Softmax reads) and then DP_TRACE_ROLE_MHA_OUT (the probabilities); then roles 0, 1, 2 for the node's output slots (QKV has three).
+ * Offsets are contiguous: the first is 0, each entry starts where the one before ends, the last ends at row_words. A Flatten node's output is
+ * entered like any other (a copy of its input). Not in the row: the model inputs (the caller has them) and derived data (the FFT tables of a
+ * Conv node, the row maxima of a Logits node). */
+#define DP_TRACE_ROLE_MHA_IN  16u
+#define DP_TRACE_ROLE_MHA_OUT 17u
+/* The layout of a model blob (as dp_model_infer_host takes it); host only. entries: 4 words per entry (node, role, offset, len), cap_entries =
+ * the entries it has room for (entries may be NULL with cap_entries 0: the call then only counts). *nentries and *row_words are always set;
+ * more entries than cap_entries: DP_ERR_ARG. */
+int32_t dp_model_trace_layout(const int64_t* model_blob, size_t nwords, uint64_t* entries, size_t cap_entries, size_t* nentries, size_t* row_words);
+/* dp_model_infer_host that returns the whole trace row instead of the outputs; host only, the yardstick of dp_model_infer_trace. In: *row_words =
+ * the capacity of `row`; out: the words of a row. The errors and messages of dp_model_infer_host. */
+int32_t dp_model_infer_host_trace(const int64_t* model_blob, size_t nwords, const int64_t* input, size_t ninput, int64_t* row, size_t* row_words);
+/* dp_model_infer_ex (reasons NULL) or dp_model_infer_checked (reasons: ninputs words) that also returns the trace row of every input: rows =
+ * ninputs x row_cap words, *row_words = the words of a row (row_cap too small: DP_ERR_ARG). Row i holds the integers of
+ * dp_model_infer_host_trace for input i; in checked mode the row of a refused input is zeros, as its output row is. The rows are gathered on the
+ * device (one launch per chunk of the batch) and come down in one copy per chunk beside the outputs; they enter the accounting of
+ * DP_INFER_SCRATCH_MB, and the `[dp infer]` line gets `; taps T entries, W words, pack_launches L pack_ms X` (in front of `; checked, ...`).
+ * Flag and kind rules, errors and messages: those of the two calls it extends. */
+int32_t dp_model_infer_trace(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags,
+                             int64_t* rows, size_t row_cap, size_t* row_words,
+                             int64_t* outputs, size_t noutput_cap, size_t* noutput,
+                             uint32_t* reasons /* nullable: checked mode */, double* wall_ms /* nullable */);
+
+/* ---- Proving from the device inference.
+ * dp_model_prove_batch with a flag word. flags == 0 and reasons == NULL: exactly dp_model_prove_batch (every input is inferred on the host, by
+ * the thread that proves it or a helper). DP_PROVE_DEVICE_INFER: the inputs are inferred on the model's GPU with taps and all kinds
+ * (dp_model_infer_trace) before any proof of theirs starts, and the host work in front of a proof shrinks to rebuilding the trace from its row and
+ * the host half of the witness generation (the Softmax shifts, the witness columns and the FFT tables of a Conv node stay host work). The proofs
+ * are word for word those of dp_model_prove_batch.
+ * The rows live in host memory: at most DP_PROVE_TRACE_MB (environment, default 4096) of them at a time. The batch is cut into segments of at most
+ * max(concurrency, budget / bytes of a row) inputs; each segment is inferred and then proved, the proofs in flight ramp up and drain once per segment.
+ * reasons (nproofs words, needs DP_PROVE_DEVICE_INFER): an input the inference refuses does not fail the batch — reasons[i] is its class
+ * (DP_INFER_BAD_*), proof_words[i] is NULL with 0 words and its output row is zeros; every other input is proved. reasons == NULL: such an input
+ * ends the call with DP_ERR_ARG and the host's message, and every proof of the batch is discarded, as in dp_model_prove_batch.
+ * wall_ms (nullable): inference + proving; infer_ms (nullable): the device inference alone (0 without the flag). Unknown flag bits, or reasons
+ * without the flag: DP_ERR_ARG. */
+#define DP_PROVE_DEVICE_INFER 1u
+int32_t dp_model_prove_batch_ex(dp_model* m, const int64_t* inputs, size_t nproofs, size_t ninput, int32_t concurrency, uint32_t flags,
+                                uint32_t* reasons /* nullable */, uint64_t** proof_words, size_t* proof_nwords,
+                                int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms /* nullable */, double* infer_ms /* nullable */);
 
 #ifdef __cplusplus
 }
