@@ -583,6 +583,14 @@ class Context:
         from .infer import infer_trace
         return infer_trace(self, inputs_i64, all_kinds=all_kinds, checked=checked)
 
+    def decode(self, prompts, prompt_lens, max_new, eos=None, pad=0, all_kinds=False):
+        """dp_model_decode: greedy decoding of a batch of prompts, the whole loop on this context's GPU (`generate` is the constructor, so the verb is
+        decode). Returns (tokens[n, seq], lengths[n], stops[n], reasons[n], outputs[n, seq], wall_ms); stops[i] is one of deep_prove_amd.infer.STOPS,
+        outputs[i] the model's output on tokens[i] — what Prover.prove(tokens[i]) proves. The model must map seq tokens (an Embeddings node first) to the
+        seq tokens a Logits node chose, without a Softmax; all_kinds as in infer()"""
+        from .infer import decode
+        return decode(self, prompts, prompt_lens, max_new, eos=eos, pad=pad, all_kinds=all_kinds)
+
     def free(self):
         if self.h:
             _lib.load().dp_model_free(self.h)
@@ -671,6 +679,16 @@ class Prover:
             outs[good] = os_
         return proofs, outs, reasons, ms
 
+    def decode_and_prove(self, prompts, prompt_lens, max_new, eos=None, pad=0, concurrency=1, all_kinds=False):
+        """Context.decode, then one proof per completion from the device inference of its final tokens (prove_batch_screened(tokens, concurrency,
+        device_infer=True)). Returns (tokens, lengths, stops, reasons, outputs, proofs); proofs[i] is None for a refused prompt, and otherwise word for
+        word Prover.prove(tokens[i]) — verify_decode(verifier_blob, proofs[i], tokens[i], outputs[i], prompt_lens[i], lengths[i], stops[i], eos, pad,
+        max_new) accepts it as the completion of its prompt"""
+        tokens, lengths, stops, reasons, outs, _ = self.ctx.decode(prompts, prompt_lens, max_new, eos=eos, pad=pad, all_kinds=all_kinds)
+        proofs, pouts, preasons, ms = self.prove_batch_screened(tokens, concurrency, device_infer=True)
+        assert ((preasons != 0) == (reasons != 0)).all() and (pouts == outs).all(), "the proved inference differs from the decoded one"
+        self.last_prove_ms = ms
+        return tokens, lengths, stops, reasons, outs, proofs
 
     def output_len(self):
         """length of the model's output tensor (dp_model_output_len)"""

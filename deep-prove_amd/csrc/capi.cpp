@@ -1,6 +1,7 @@
 // extern "C" surface of libdeepprove_hip.so (declared in include/deep_prove_hip.h).
 #include "../../include/deep_prove_hip.h"
 #include "../../include/deep_prove_hip_infer.h"
+#include "../../include/deep_prove_hip_decode.h"
 #include "../../include/deep_prove_hip_peer.h"
 #include "zkml.h"
 #include "blob.h"
@@ -1668,6 +1669,96 @@ int32_t dp_model_infer_ex(dp_model* m, const int64_t* inputs, size_t ninputs, si
 int32_t dp_model_infer_checked(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, size_t* nrefused, double* wall_ms) {
   if (!reasons) return guard([] { throw DpError(DP_ERR_ARG, "bad arguments"); });
   return model_infer(m, inputs, ninputs, ninput, flags, outputs, noutput_cap, noutput, reasons, nrefused, wall_ms);
+}
+// ---- decode (include/deep_prove_hip_decode.h): the semantics are decode_step's (infer.h), for the device loop and the host loop alike
+static_assert(DP_DECODE_STOP_EOS == DECODE_STOP_EOS && DP_DECODE_STOP_WINDOW == DECODE_STOP_WINDOW && DP_DECODE_STOP_MAX_NEW == DECODE_STOP_MAX_NEW && DP_DECODE_STOP_REFUSED == DECODE_STOP_REFUSED, "deep_prove_hip_decode.h and infer.h");
+// what the call itself can get wrong, for a model whose window and vocabulary are known
+static void decode_check_call(size_t seq, size_t vocab, const uint32_t* prompt_len, size_t nprompts, int64_t pad) {
+  DP_REQUIRE(pad >= 0 && (uint64_t)pad < vocab, DP_ERR_ARG, "dp_model_decode: pad " + std::to_string(pad) + " lies outside the vocabulary of " + std::to_string(vocab) + " tokens");
+  for (size_t i = 0; i < nprompts; i++)
+    DP_REQUIRE(prompt_len[i] >= 1 && prompt_len[i] <= seq, DP_ERR_ARG, "dp_model_decode: prompt_len " + std::to_string(prompt_len[i]) + " of prompt " + std::to_string(i) + " lies outside 1.." + std::to_string(seq));
+}
+// the class (DP_INFER_BAD_*) of a refusal of run_model, by the layer its message names; 0: not a refusal of the data
+static uint32_t decode_refusal_class(const DpError& e) {
+  if (e.code != DP_ERR_ARG) return DP_INFER_OK;
+  const std::string w = e.what();
+  static const std::pair<const char*, uint32_t> heads[] = {{"requant: value exceeds", DP_INFER_BAD_REQUANT}, {"embeddings: token outside", DP_INFER_BAD_TOKEN}, {"gelu: input out of range", DP_INFER_BAD_GELU},
+                                                           {"layernorm: input out of range", DP_INFER_BAD_LAYERNORM}, {"layernorm: the inverse square root", DP_INFER_BAD_LAYERNORM}, {"softmax: input out of range", DP_INFER_BAD_SOFTMAX}};
+  for (const auto& h : heads) if (w.rfind(h.first, 0) == 0) return h.second;
+  return DP_INFER_OK;
+}
+int32_t dp_model_decode(dp_model* m, const int64_t* prompts, const uint32_t* prompt_len, size_t nprompts, uint32_t max_new, int64_t eos, int64_t pad, uint32_t flags,
+                        int64_t* tokens, uint32_t* length, uint32_t* stop, uint32_t* reasons, int64_t* outputs, double* wall_ms) {
+  return guard([&] {
+    DP_REQUIRE(m && (!nprompts || (prompts && prompt_len && tokens && length && stop && reasons)), DP_ERR_ARG, "bad arguments");
+    DP_REQUIRE(!(flags & ~(uint32_t)DP_INFER_ALL_KINDS), DP_ERR_ARG, "dp_model_decode: unknown flag bits");
+    const ModelSpec& spec = m->zk->model;
+    size_t vocab = 0;
+    const size_t seq = decode_window(spec, &vocab);
+    decode_check_call(seq, vocab, prompt_len, nprompts, pad);
+    CtxLock lk(m->ctx);
+    std::unique_ptr<InferProgram>& prog = m->infer_prog[flags];
+    if (!prog) prog.reset(new InferProgram(infer_plan(spec, flags)));  // (flags 0: refuses a GELU node before any device work)
+    if (wall_ms) *wall_ms = 0;
+    if (!nprompts) return;
+    if (!m->infer_state[flags]) m->infer_state[flags] = hip_infer_state_new(m->ctx->device_id);
+    hip_infer_decode(m->ctx->dev, *prog, m->infer_state[flags], prompts, prompt_len, nprompts, max_new, eos, pad, tokens, length, stop, reasons, outputs, wall_ms);
+  });
+}
+int32_t dp_model_decode_host(const int64_t* model_blob, size_t nwords, const int64_t* prompt, uint32_t prompt_len, uint32_t max_new, int64_t eos, int64_t pad,
+                             int64_t* tokens, uint32_t* length, uint32_t* stop, uint32_t* reason, int64_t* output) {
+  return guard([&] {
+    DP_REQUIRE(model_blob && prompt && tokens && length && stop && reason, DP_ERR_ARG, "bad arguments");
+    const ModelSpec m = host_model(model_blob, nwords);
+    size_t vocab = 0;
+    const size_t seq = decode_window(m, &vocab);
+    decode_check_call(seq, vocab, &prompt_len, 1, pad);
+    std::vector<int64_t> tok(seq, pad), out(seq, 0);
+    std::copy(prompt, prompt + prompt_len, tok.begin());
+    const uint32_t limit = (uint32_t)std::min<size_t>(seq, (size_t)prompt_len + max_new);
+    uint32_t len = prompt_len, st = 0, cls = DP_INFER_OK;
+    // the inference of the window as it stands: false (and the class) when run_model refuses the data
+    auto infer = [&] {
+      try { out = model_output(m, run_model(m, tok)); return true; }
+      catch (const DpError& e) { if (!(cls = decode_refusal_class(e))) throw; return false; }
+    };
+    while (!st) {
+      if (!decode_limit(len, limit, (uint32_t)seq)) infer();  // (a limit stops the prompt before it is inferred)
+      decode_step(len, st, limit, (uint32_t)seq, eos, cls, out.data(), tok.data());
+    }
+    // the output of the final tokens: a pass of its own (after EOS it repeats the last one; after an append it is new)
+    if (!cls && !infer()) st = DP_DECODE_STOP_REFUSED;
+    if (cls) std::fill(out.begin(), out.end(), int64_t(0));
+    memcpy(tokens, tok.data(), seq * 8);
+    *length = len; *stop = st; *reason = cls;
+    if (output) memcpy(output, out.data(), seq * 8);
+  });
+}
+int32_t dp_verify_decode(const uint64_t* vb, size_t vn, const uint64_t* pw, size_t pn, const int64_t* tokens, size_t seq, const int64_t* output,
+                         uint32_t prompt_len, uint32_t length, uint32_t stop, int64_t eos, int64_t pad, uint32_t max_new) {
+  const int32_t rc = guard([&] {
+    DP_REQUIRE(vb && pw && tokens && output, DP_ERR_ARG, "bad arguments");
+    const size_t pl = prompt_len, len = length, limit = (size_t)prompt_len + max_new;
+    const std::string head = "dp_verify_decode: ";
+    DP_REQUIRE(pl >= 1 && pl <= len && len <= seq, DP_ERR_VERIFY, head + "1 <= prompt_len <= length <= seq does not hold (prompt_len " + std::to_string(pl) + ", length " + std::to_string(len) + ", seq " + std::to_string(seq) + ")");
+    for (size_t t = pl - 1; t + 2 <= len; t++)
+      DP_REQUIRE(output[t] == tokens[t + 1], DP_ERR_VERIFY, head + "token " + std::to_string(t + 1) + " is not the one the model chose at position " + std::to_string(t) + " (" + std::to_string(tokens[t + 1]) + ", chosen " + std::to_string(output[t]) + ")");
+    for (size_t t = pl - 1; t + 2 <= len; t++)
+      DP_REQUIRE(eos < 0 || output[t] != eos, DP_ERR_VERIFY, head + "the end-of-sequence token was chosen at position " + std::to_string(t) + " and decoding went on");
+    for (size_t t = len; t < seq; t++)
+      DP_REQUIRE(tokens[t] == pad, DP_ERR_VERIFY, head + "token " + std::to_string(t) + " behind the completion is not the pad token (" + std::to_string(tokens[t]) + ")");
+    if (stop == DP_DECODE_STOP_EOS) {
+      DP_REQUIRE(len < seq, DP_ERR_VERIFY, head + "stop EOS claimed for a full window (length " + std::to_string(len) + ")");
+      DP_REQUIRE(len < limit, DP_ERR_VERIFY, head + "stop EOS claimed at length " + std::to_string(len) + " == prompt_len + max_new");
+      DP_REQUIRE(eos >= 0 && output[len - 1] == eos, DP_ERR_VERIFY, head + "stop EOS claimed, but the model chose " + std::to_string(output[len - 1]) + " at position " + std::to_string(len - 1));
+    } else if (stop == DP_DECODE_STOP_WINDOW) {
+      DP_REQUIRE(len == seq, DP_ERR_VERIFY, head + "stop WINDOW claimed at length " + std::to_string(len) + " of " + std::to_string(seq));
+    } else if (stop == DP_DECODE_STOP_MAX_NEW) {
+      DP_REQUIRE(len == limit, DP_ERR_VERIFY, head + "stop MAX_NEW claimed at length " + std::to_string(len) + ", prompt_len + max_new is " + std::to_string(limit));
+      DP_REQUIRE(len < seq, DP_ERR_VERIFY, head + "stop MAX_NEW claimed for a full window (length " + std::to_string(len) + "): that is WINDOW");
+    } else throw DpError(DP_ERR_VERIFY, head + (stop == DP_DECODE_STOP_REFUSED ? "a refused prompt (stop REFUSED) is never verifiable" : "unknown stop reason " + std::to_string(stop)));
+  });
+  return rc != DP_OK ? rc : dp_verify(vb, vn, pw, pn, tokens, seq, output, seq);
 }
 int32_t dp_host_poseidon2(uint64_t state[8], int32_t force_scalar, int32_t* vectorised) {
   return guard([&] {

@@ -83,7 +83,55 @@ void hip_infer_state_free(InferDeviceState* s);
 void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* inputs, size_t ninputs, int64_t* outputs, size_t out_stride, double* wall_ms, uint32_t* reasons = nullptr,
                    int64_t* rows = nullptr, size_t row_stride = 0);
 
+// ---- Decode (dp_model_decode, include/deep_prove_hip_decode.h): greedy generation for a model that maps `seq` tokens to the `seq` tokens its
+// Logits node chose. The state of one prompt is (tokens[seq], length, stop); limit = prompt_len + max_new (never above seq). One step: test
+// the limits, infer the whole padded window, take out[length - 1]; the end-of-sequence token stops the prompt and is NOT appended, any other
+// token is. decode_step below is that step for one prompt, given the inference of its tokens; the host loop (dp_model_decode_host) and
+// k_infer_next_token (infer_kernels.inc) both call it.
+constexpr uint32_t DECODE_STOP_EOS = 1, DECODE_STOP_WINDOW = 2, DECODE_STOP_MAX_NEW = 3, DECODE_STOP_REFUSED = 4;  // (DP_DECODE_STOP_* of the public header; 0: still decoding)
+// the limits alone (steps 1 and 2): what stops a prompt of this length before any inference, or 0. (length 0 is refused by every caller; it
+// stops here so that no index is ever formed from it)
+DP_HD uint32_t decode_limit(uint32_t length, uint32_t limit, uint32_t seq) {
+  return length == 0 || length >= seq ? DECODE_STOP_WINDOW : length >= limit ? DECODE_STOP_MAX_NEW : 0;
+}
+// One step of one prompt. status: the status word of the inference of `tokens` (INFER_OK or a class: the prompt is refused as it stands);
+// out: the Logits row of that inference, read at length - 1 only, and only when no limit stops the prompt first (a caller that knows
+// decode_limit() != 0 need not infer: out is not read then). The token goes to tokens[length] once length < seq is established, and the limits
+// are tested again on the new length: that is the head of the next step, taken here so that a prompt never costs an inference it cannot use.
+// A prompt whose stop is set is left alone.
+DP_HD void decode_step(uint32_t& length, uint32_t& stop, uint32_t limit, uint32_t seq, int64_t eos, uint32_t status, const int64_t* out, int64_t* tokens) {
+  if (stop) return;
+  if (status) { stop = DECODE_STOP_REFUSED; return; }
+  if ((stop = decode_limit(length, limit, seq))) return;
+  const int64_t t = out[length - 1];  // (1 <= length < seq)
+  if (eos >= 0 && t == eos) { stop = DECODE_STOP_EOS; return; }
+  tokens[length] = t;
+  length += 1;
+  stop = decode_limit(length, limit, seq);
+}
+// prompts: nprompts x seq words (row i read up to prompt_len[i]); tokens, outputs (nullable): nprompts x seq; length, stop, reasons: nprompts
+// words. The caller has checked that p is decodable (seq = p.input_len = p.output_len, one input, one output, no IO_SOFTMAX), 1 <= prompt_len
+// <= seq and pad. Throws DpError.
+void hip_infer_decode(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* prompts, const uint32_t* prompt_len, size_t nprompts, uint32_t max_new, int64_t eos, int64_t pad,
+                      int64_t* tokens, uint32_t* length, uint32_t* stop, uint32_t* reasons, int64_t* outputs, double* wall_ms);
+
 #ifdef DP_INFER_PLANNER  // (capi.cpp, after zkml.h)
+// Whether dp_model_decode can drive the model: the length of its window, or DP_ERR_ARG with the condition that fails. vocab: the Embeddings vocabulary
+inline size_t decode_window(const ModelSpec& m, size_t* vocab) {
+  DP_REQUIRE(input_tensor_lens(m).size() == 1, DP_ERR_ARG, "dp_model_decode: the model must have exactly one input tensor (it has " + std::to_string(input_tensor_lens(m).size()) + ")");
+  const size_t seq = m.input_len;
+  const std::vector<Edge> e0 = m.layers.empty() ? std::vector<Edge>() : edges_in(m, 0);
+  DP_REQUIRE(!m.layers.empty() && m.layers[0].kind == L_EMBED && e0.size() == 1 && e0[0].from < 0 && e0[0].slot == 0, DP_ERR_ARG, "dp_model_decode: node 0 must be an Embeddings layer that reads the input tokens");
+  const std::vector<Edge> outs = output_edges(m);
+  DP_REQUIRE(outs.size() == 1 && outs[0].from >= 0 && m.layers[(size_t)outs[0].from].kind == L_LOGITS, DP_ERR_ARG, "dp_model_decode: the only output of the model must be a Logits node");
+  const LayerSpec& lg = m.layers[(size_t)outs[0].from];
+  DP_REQUIRE(lg.nrows == seq, DP_ERR_ARG, "dp_model_decode: the Logits node must choose one token per input position (rows " + std::to_string(lg.nrows) + ", window " + std::to_string(seq) + ")");
+  DP_REQUIRE(lg.ncols <= m.layers[0].nrows, DP_ERR_ARG, "dp_model_decode: the Logits node chooses among " + std::to_string(lg.ncols) + " tokens, the Embeddings vocabulary has " + std::to_string(m.layers[0].nrows));
+  for (size_t id = 0; id < m.layers.size(); id++)
+    DP_REQUIRE(m.layers[id].kind != L_SOFTMAX && m.layers[id].kind != L_MHA, DP_ERR_ARG, "dp_model_decode: node " + std::to_string(id) + " holds a Softmax, whose row shifts need a host step in every decode step: not decodable yet");
+  if (vocab) *vocab = m.layers[0].nrows;
+  return seq;
+}
 inline const char* infer_kind_name(int k) {
   static const char* names[] = {"Dense", "Requant", "ReLU", "Conv", "MaxPool", "Flatten", "MatMul", "Add", "Embeddings", "Positional", "MatMul2", "Add2", "ConcatMatMul", "QKV", "LayerNorm", "Softmax", "Mha", "GELU", "Logits"};
   return k >= 0 && k < 19 ? names[k] : "unknown";

@@ -277,6 +277,20 @@ __global__ __launch_bounds__(256) void k_infer_tap_pack(const InferTapDesc* __re
     for (size_t j = i0; j < n; j += step) { const size_t s = j / t.len, e = j - s * t.len; dst[s * row_words + e] = t.src[j]; }
   }
 }
+// Decode: the next token of every sample of the chunk, after the ops of a step (decode_step of infer.h, the function the host loop calls). One
+// thread per sample. out: the Logits tensor [nb][seq] of this step's inference; tokens: the int64 input block of the chunk [nb][seq], which the
+// next step's k_infer_load reads; length, stop, limit: one word per sample; status: the chunk's status words, only read here. A sample whose stop
+// is set is left alone, one whose status word is set becomes REFUSED and keeps its tokens. Plain loads and stores in stream order, no atomics.
+// In bounds: i < nb; out is read at length - 1 and tokens written at length only once 1 <= length < seq holds (decode_limit).
+__global__ __launch_bounds__(256) void k_infer_next_token(const int64_t* __restrict__ out, int64_t* __restrict__ tokens, unsigned* __restrict__ length, unsigned* __restrict__ stop,
+                                                          const unsigned* __restrict__ limit, const unsigned* __restrict__ status, size_t nb, unsigned seq, int64_t eos) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nb) return;
+  uint32_t len = length[i], st = stop[i];
+  if (st) return;
+  decode_step(len, st, limit[i], seq, eos, status[i], out + i * seq, tokens + i * seq);
+  length[i] = len; stop[i] = st;
+}
 
 struct InferDeviceState {
   int device = 0;
@@ -312,10 +326,12 @@ struct InferScratch {
   unsigned* status() const { return (unsigned*)(dev + off_stat); }
   uint32_t* sm_status() const { return (uint32_t*)(pinned + sm_in); }
 };
+// (inputs null: the input block is int64 whatever it will hold — decode rewrites it on the device)
 static InferScratch infer_layout(const InferProgram& p, const int64_t* inputs, size_t ninputs, bool taps) {
   const char* mbs = getenv("DP_INFER_SCRATCH_MB");
   const size_t scratch_cap = (mbs && atoll(mbs) > 0 ? (size_t)atoll(mbs) : size_t(1024)) << 20, nt = p.tensors.size();
   InferScratch m;
+  if (!inputs) m.in_q = false;
   for (size_t i = 0, n = ninputs * p.input_len; i < n && m.in_q; i++) m.in_q = inputs[i] >= -128 && inputs[i] <= 127;
   m.q.resize(nt); m.off64.resize(nt); m.off8.resize(nt);
   size_t per_sample = 0;
@@ -395,6 +411,27 @@ static void infer_shift_trip(const InferProgram& p, const InferOp& o, const Infe
   HIP_CHECK(hipMemcpyAsync(m.status(), m.sm_status(), nb * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(m.T64(o.in1), shifts, nsh * 8, hipMemcpyHostToDevice, s));
 }
+// The program for the nb samples of the chunk whose input block is on the device: the loads of the model inputs, then every op in order, with
+// the round trip in front of each IO_SOFTMAX (the only host synchronisation here: a program without one is enqueued and nothing waits).
+// Plain mode (not checked): the class of the refused sample a shift step found, which ends the call; the later ops are not enqueued then
+static uint32_t infer_enqueue(const InferProgram& p, const InferScratch& m, InferDeviceState* st, hipStream_t s, size_t nb, bool checked, size_t* launches, size_t& trips, double& trip_ms) {
+  size_t ioff = 0;
+  for (int t : p.inputs) {
+    const size_t len = p.tensors[(size_t)t].len, n = nb * len;
+    k_infer_load<<<infer_grid(n), 256, 0, s>>>(m.in_q ? nullptr : (const int64_t*)(m.dev + m.off_in), m.in_q ? (const int8_t*)(m.dev + m.off_in) : nullptr, p.input_len, ioff, len, m.T64(t), m.T8(t), n);
+    ioff += len; launches[IO_KINDS]++;
+  }
+  for (const InferOp& o : p.ops) {
+    if (o.kind == IO_SOFTMAX) {
+      const auto ts = std::chrono::steady_clock::now();
+      infer_shift_trip(p, o, m, s, nb);
+      trips++; trip_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
+      if (!checked) if (const uint32_t cls = infer_first_class(m.sm_status(), nb)) return cls;
+    }
+    infer_launch(p, o, m, st, s, nb, launches);
+  }
+  return INFER_OK;
+}
 void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* inputs, size_t ninputs, int64_t* outputs, size_t out_stride, double* wall_ms, uint32_t* reasons,
                    int64_t* rows, size_t row_stride) {
   HipDev* hd = static_cast<HipDev*>(d);
@@ -437,22 +474,7 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
       else memcpy(m.pinned, inputs + b0 * p.input_len, nin * 8);
       HIP_CHECK(hipMemcpyAsync(m.dev + m.off_in, m.pinned, nin * in_w, hipMemcpyHostToDevice, s));
       HIP_CHECK(hipMemsetAsync(m.status(), 0, nb * 4, s));
-      size_t ioff = 0;
-      for (int t : p.inputs) {
-        const size_t len = p.tensors[(size_t)t].len, n = nb * len;
-        k_infer_load<<<infer_grid(n), 256, 0, s>>>(m.in_q ? nullptr : (const int64_t*)(m.dev + m.off_in), m.in_q ? (const int8_t*)(m.dev + m.off_in) : nullptr, p.input_len, ioff, len, m.T64(t), m.T8(t), n);
-        ioff += len; launches[IO_KINDS]++;
-      }
-      for (const InferOp& o : p.ops) {
-        if (o.kind == IO_SOFTMAX) {
-          const auto ts = std::chrono::steady_clock::now();
-          infer_shift_trip(p, o, m, s, nb);
-          trips++; trip_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
-          if (!reasons && (stop = infer_first_class(m.sm_status(), nb))) break;
-        }
-        infer_launch(p, o, m, st, s, nb, launches);
-      }
-      if (stop) break;
+      if ((stop = infer_enqueue(p, m, st, s, nb, reasons != nullptr, launches, trips, trip_ms))) break;
       size_t ooff = 0;
       for (int t : p.outputs) {
         const size_t len = p.tensors[(size_t)t].len, n = nb * len;
@@ -495,4 +517,102 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
                    taps ? ("; taps " + std::to_string(p.taps.size()) + " entries, " + std::to_string(p.row_words) + " words, pack_launches " + std::to_string(tap_launches) + " pack_ms " + std::to_string(tap_ms)).c_str() : "",
                    reasons ? ("; checked, refused " + std::to_string(nrefused)).c_str() : "");
   DP_REQUIRE(!stop, DP_ERR_ARG, INFER_REFUSAL[stop]);
+}
+// dp_model_decode: greedy generation for a batch of prompts, on the device from the upload of the prompts to the download of the completions.
+// Per chunk (DP_INFER_SCRATCH_MB, as hip_infer_run): the token block [nb][seq] (the prompts, `pad` behind them; always int64: k_infer_next_token
+// rewrites it) and the state (length, stop, limit per sample) go up once; then step after step is enqueued — the program (infer_enqueue: a
+// decodable program holds no IO_SOFTMAX, so nothing in a step waits for the host), then k_infer_next_token. The number of steps is known in
+// advance: the most tokens a sample of the chunk can still take. Every DECODE_POLL_STEPS steps the 4-byte stop words come down, and the chunk
+// ends early when all are set. Then ONE more pass of the program over the final tokens gives the outputs (what a proof of tokens[i] carries),
+// and outputs, tokens, lengths, stops and status words come down behind one synchronisation. The status words are never cleared between the
+// steps: a refused sample stays refused (its stop is REFUSED and its tokens stay as they were), every other sample's word is zero. A sample the
+// final pass refuses is REFUSED as well, with zeros for its outputs.
+constexpr size_t DECODE_POLL_STEPS = 4;
+void hip_infer_decode(Dev* d, const InferProgram& p, InferDeviceState* st, const int64_t* prompts, const uint32_t* prompt_len, size_t nprompts, uint32_t max_new, int64_t eos, int64_t pad,
+                      int64_t* tokens, uint32_t* length, uint32_t* stop, uint32_t* reasons, int64_t* outputs, double* wall_ms) {
+  HipDev* hd = static_cast<HipDev*>(d);
+  hd->bind_thread(); hd->sync();
+  hipStream_t s = hd->stream();
+  static const bool timing = getenv("DP_TIMING") && atoi(getenv("DP_TIMING"));
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t seq = p.input_len;
+  DP_REQUIRE(seq >= 1 && seq < (size_t(1) << 31) && p.output_len == seq && p.inputs.size() == 1 && p.outputs.size() == 1, DP_ERR_ARG, "dp_model_decode: the program is not decodable");
+  for (const InferOp& o : p.ops) DP_REQUIRE(o.kind != IO_SOFTMAX, DP_ERR_ARG, "dp_model_decode: the program holds a Softmax");
+  InferScratch m = infer_layout(p, nullptr, nprompts, false);
+  const size_t chunk = m.chunk;
+  const auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+  // the state of the chunk on the device: [length][stop][limit], chunk words each; the pinned block: [outputs][tokens][length][stop][status] on
+  // the way down (the tokens and the three state arrays at the same places on the way up)
+  const size_t tok_bytes = up(chunk * seq * 8), word_bytes = up(chunk * 4);
+  char* dstate = nullptr; char* pin = nullptr;
+  st->c64.resize(p.consts.size(), nullptr); st->c8.resize(p.consts.size(), nullptr);
+  size_t launches[IO_KINDS + 3] = {0}, nchunks = 0, nsteps = 0, nlaunch = 0, npolls = 0, trips = 0;
+  double trip_ms = 0, final_ms = 0;
+  auto cleanup = [&] {
+    (void)hipStreamSynchronize(s);
+    if (m.dev) (void)hipFree(m.dev); if (dstate) (void)hipFree(dstate); if (pin) (void)hipHostFree(pin);
+    m.dev = nullptr; dstate = pin = nullptr;
+  };
+  try {
+    HIP_CHECK(hipMalloc((void**)&m.dev, m.total));
+    HIP_CHECK(hipMalloc((void**)&dstate, 3 * word_bytes));
+    HIP_CHECK(hipHostMalloc((void**)&pin, 2 * tok_bytes + 3 * word_bytes, hipHostMallocDefault));
+    int64_t* dtok = (int64_t*)(m.dev + m.off_in);
+    unsigned* dlen = (unsigned*)dstate; unsigned* dstop = (unsigned*)(dstate + word_bytes); unsigned* dlim = (unsigned*)(dstate + 2 * word_bytes);
+    int64_t* hout = (int64_t*)pin; int64_t* htok = (int64_t*)(pin + tok_bytes);
+    uint32_t* hlen = (uint32_t*)(pin + 2 * tok_bytes); uint32_t* hstop = (uint32_t*)(pin + 2 * tok_bytes + word_bytes); uint32_t* hlim = (uint32_t*)(pin + 2 * tok_bytes + 2 * word_bytes);
+    const int64_t* dout = m.T64(p.outputs[0]);  // (the Logits tensor, [nb][seq]: the layout of the output rows)
+    for (size_t b0 = 0; b0 < nprompts; b0 += chunk) {
+      const size_t nb = std::min(chunk, nprompts - b0);
+      nchunks++;
+      size_t steps = 0;  // the most tokens a sample of the chunk can take
+      for (size_t i = 0; i < nb; i++) {
+        const uint32_t pl = prompt_len[b0 + i], lim = (uint32_t)std::min<size_t>(seq, (size_t)pl + max_new);
+        for (size_t j = 0; j < seq; j++) htok[i * seq + j] = j < pl ? prompts[(b0 + i) * seq + j] : pad;
+        hlen[i] = pl; hlim[i] = lim; hstop[i] = decode_limit(pl, lim, (uint32_t)seq);
+        steps = std::max<size_t>(steps, lim - pl);
+      }
+      HIP_CHECK(hipMemcpyAsync(dtok, htok, nb * seq * 8, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(dlen, hlen, nb * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(dstop, hstop, nb * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(dlim, hlim, nb * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemsetAsync(m.status(), 0, nb * 4, s));
+      for (size_t k = 0; k < steps; k++) {
+        (void)infer_enqueue(p, m, st, s, nb, true, launches, trips, trip_ms);
+        k_infer_next_token<<<infer_grid(nb), 256, 0, s>>>(dout, dtok, dlen, dstop, dlim, m.status(), nb, (unsigned)seq, eos);
+        nsteps++; nlaunch++;
+        if ((k + 1) % DECODE_POLL_STEPS == 0 && k + 1 < steps) {  // (the copy up of the state has landed long ago: hstop is free)
+          HIP_CHECK(hipGetLastError());
+          HIP_CHECK(hipMemcpyAsync(hstop, dstop, nb * 4, hipMemcpyDeviceToHost, s));
+          HIP_CHECK(hipStreamSynchronize(s));
+          npolls++;
+          if (std::find(hstop, hstop + nb, 0u) == hstop + nb) break;
+        }
+      }
+      const auto tf = std::chrono::steady_clock::now();
+      (void)infer_enqueue(p, m, st, s, nb, true, launches, trips, trip_ms);
+      HIP_CHECK(hipGetLastError());
+      uint32_t* hstat = hlim;  // (the limits are not needed again: the status words come down in their place)
+      HIP_CHECK(hipMemcpyAsync(hout, dout, nb * seq * 8, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(htok, dtok, nb * seq * 8, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(hlen, dlen, nb * 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(hstop, dstop, nb * 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(hstat, m.status(), nb * 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      final_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tf).count();
+      for (size_t i = 0; i < nb; i++) {
+        const uint32_t cls = hstat[i] == INFER_BAD_LAYERNORM_TABLE ? INFER_BAD_LAYERNORM : hstat[i];
+        DP_REQUIRE(cls || hstop[i], DP_ERR_ARG, "dp_model_decode: a prompt is still decoding after its last step");
+        memcpy(tokens + (b0 + i) * seq, htok + i * seq, seq * 8);
+        length[b0 + i] = hlen[i]; stop[b0 + i] = cls ? DECODE_STOP_REFUSED : hstop[i]; reasons[b0 + i] = cls;
+        if (outputs && cls) memset(outputs + (b0 + i) * seq, 0, seq * 8);
+        else if (outputs) memcpy(outputs + (b0 + i) * seq, hout + i * seq, seq * 8);
+      }
+    }
+  } catch (...) { cleanup(); throw; }
+  cleanup();
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (wall_ms) *wall_ms = ms;
+  for (size_t k = 0; k < IO_KINDS + 2; k++) nlaunch += launches[k];  // (launches[IO_KINDS + 2] counts the i8 form of launches counted under IO_GEMM)
+  if (timing) fprintf(stderr, "[dp decode] prompts %zu chunks %zu steps %zu launches %zu polls %zu final_ms %.3f\n", nprompts, nchunks, nsteps, nlaunch, npolls, final_ms);
 }

@@ -138,3 +138,7 @@ pub use infer::{dp_model_infer, dp_model_infer_checked, dp_model_infer_ex, DP_IN
 /// `include/deep_prove_hip_peer.h`: the sharded sumcheck between processes, shares through peer-mapped mailboxes (`dp_peer_*`), in a module of its own.
 pub mod peer;
 pub use peer::{dp_peer, dp_peer_connect, dp_peer_create, dp_peer_free, dp_sumcheck_prove_peer, DP_PEER_HANDLE_BYTES};
+
+/// `include/deep_prove_hip_decode.h`: greedy decoding on the device and the verifier that accepts a proof as a completion, in a module of its own.
+pub mod decode;
+pub use decode::{dp_model_decode, dp_model_decode_host, dp_verify_decode};
