@@ -7,6 +7,9 @@
 #include "blob.h"
 #include "sharded.h"
 #include "fiber.h"
+#include "hip_host.h"
+#include "batch_plan.h"
+#include "prep_ahead.h"
 #define DP_INFER_PLANNER
 #include "infer.h"
 #include <dlfcn.h>
@@ -28,8 +31,6 @@
 #include <unistd.h>
 
 DP_FIBER_SWITCH_ASM
-namespace dp { struct Cohort; Cohort* hip_cohort_new(); void hip_cohort_lead(Cohort* c, size_t n); void hip_cohort_follow(Cohort* c, Cohort* leader); void hip_cohort_free(Cohort* c); void hip_cohort_drain(Cohort* c); void hip_cohort_stats(Cohort* c, size_t* fired, size_t* packs); void hip_dev_cohort_attach(Dev* d, Cohort* c); void hip_dev_cohort_detach(Dev* d); void hip_dev_set_latency_mode(Dev* d, bool on); void hip_dev_pcs_share(Dev* worker, Dev* owner); void hip_dump_wg_times(); void hip_dev_dump_host_stats(Dev* d); size_t hip_dev_arena_peak(Dev* d); double hip_dev_probe_compress_rate(Dev* d, size_t nodes, int reps); void hip_dev_arena_peak_reset(Dev* d); void hip_mem_info(int device, size_t* free_bytes, size_t* total_bytes); void hip_dev_dump_sc_debug(Dev* d); Dev* make_hip_worker(int device, size_t arena_bytes); Dev* make_hip_dev(int device); void hip_dev_profile_enable(Dev* d, bool on); std::string hip_dev_profile_report(Dev* d);
-void hip_dev_peer_all_gather(Dev* d, const Dev::PeerMailboxes* pm, const u64* send, size_t nwords, u64* out); }
 using namespace dp;
 
 // `mu`: PCS::commit is called from rayon workers in the reference (zkml/src/commit/context.rs:79-103 into_par_iter over
@@ -729,9 +730,7 @@ int32_t dp_pcs_verify(size_t max_poly_size, const uint64_t root[4], uint32_t num
     DP_REQUIRE(t, DP_ERR_ARG, "a non-trivial opening needs the transcript");
     VerifierParams vp; vp.full_log = dp_ceil_log2(max_poly_size);
     std::vector<MerkleJob> jobs;  // (the 200 x (rounds + 1) paths are recorded, then authenticated together: eight side by side on AVX-512 CPUs)
-    merkle_sink() = &jobs;
-    try { pcs_verify(vp, c, read_point(point, num_vars), read_point(eval, 1)[0], p, t->t); } catch (...) { merkle_sink() = nullptr; throw; }
-    merkle_sink() = nullptr;
+    { MerkleRecording rec(jobs); pcs_verify(vp, c, read_point(point, num_vars), read_point(eval, 1)[0], p, t->t); }
     DP_REQUIRE(merkle_jobs_ok(jobs, verify_threads()), DP_ERR_VERIFY, "merkle path does not authenticate against the root");
   });
 }
@@ -769,9 +768,7 @@ int32_t dp_pcs_batch_verify(size_t max_poly_size, const uint64_t* roots, const u
     DP_REQUIRE(r.pos == proof_nwords, DP_ERR_ARG, "proof stream: trailing words");
     VerifierParams vp; vp.full_log = dp_ceil_log2(max_poly_size);
     std::vector<MerkleJob> jobs;
-    merkle_sink() = &jobs;
-    try { pcs_batch_verify(vp, vc, p, t->t); } catch (...) { merkle_sink() = nullptr; throw; }
-    merkle_sink() = nullptr;
+    { MerkleRecording rec(jobs); pcs_batch_verify(vp, vc, p, t->t); }
     DP_REQUIRE(merkle_jobs_ok(jobs, verify_threads()), DP_ERR_VERIFY, "merkle path does not authenticate against the root");
   });
 }
@@ -974,9 +971,7 @@ int32_t dp_async_create(dp_ctx* ctx, int32_t max_in_flight, size_t worker_arena_
       try { hip_dev_pcs_share(w.get(), ctx->dev); } catch (const DpError&) {}  // (no dp_pcs_setup yet: the PCS calls of this engine will say so)
       a->free_workers.push_back(w.get()); a->workers.push_back(std::move(w));
     }
-    const char* te = getenv("DP_HOST_THREADS");
-    size_t nth = te ? (size_t)std::max(1, atoi(te)) : (size_t)std::max(1.0, host_cpu_budget() - 2.0);
-    nth = std::min<size_t>(std::min<size_t>(nth, 22), a->max_in_flight);
+    const size_t nth = std::min<size_t>(std::min<size_t>(default_host_threads(env_host_threads(), host_cpu_budget()), 22), a->max_in_flight);
     for (size_t i = 0; i < nth; i++) a->threads.emplace_back(async_thread, a.get());
     *out = a.release();
   });
@@ -1012,7 +1007,7 @@ int32_t dp_ctx_route_to_engine(dp_ctx* ctx, dp_async* engine) {
 }
 int32_t dp_async_destroy(dp_async* a) {
   return guard([&] {
-    if (a && getenv("DP_TIMING") && atoi(getenv("DP_TIMING")) && a->njobs.load())
+    if (a && timing_on() && a->njobs.load())
       fprintf(stderr, "[dp timing] async engine: %zu calls in %zu groups (%zu merged); per call %.1f us queued before it ran, %.1f us inside\n", a->njobs.load(), a->ngroups.load(), a->nmerged.load(),
               (double)a->queue_us.load() / (double)a->njobs.load(), (double)a->body_us.load() / (double)a->njobs.load());
     delete a;
@@ -1190,9 +1185,7 @@ int32_t dp_pcs_batch_verify_evals(size_t max_poly_size, const uint64_t* roots, c
     DP_REQUIRE(r.pos == proof_nwords, DP_ERR_ARG, "proof stream: trailing words");
     VerifierParams vp; vp.full_log = dp_ceil_log2(max_poly_size);
     std::vector<MerkleJob> jobs;
-    merkle_sink() = &jobs;
-    try { pcs_batch_verify_evals(vp, cs, pts, evals, p, t->t); } catch (...) { merkle_sink() = nullptr; throw; }
-    merkle_sink() = nullptr;
+    { MerkleRecording rec(jobs); pcs_batch_verify_evals(vp, cs, pts, evals, p, t->t); }
     DP_REQUIRE(merkle_jobs_ok(jobs, verify_threads()), DP_ERR_VERIFY, "merkle path does not authenticate against the root");
   });
 }
@@ -1246,9 +1239,7 @@ int32_t dp_pcs_simple_batch_verify(size_t max_poly_size, const uint64_t root[4],
     VerifierParams vp; vp.full_log = dp_ceil_log2(max_poly_size);
     Transcript scratch;
     std::vector<MerkleJob> jobs;
-    merkle_sink() = &jobs;
-    try { pcs_simple_batch_verify(vp, c, read_point(point, num_vars), read_point(evals, (unsigned)n), p, t ? t->t : scratch); } catch (...) { merkle_sink() = nullptr; throw; }
-    merkle_sink() = nullptr;
+    { MerkleRecording rec(jobs); pcs_simple_batch_verify(vp, c, read_point(point, num_vars), read_point(evals, (unsigned)n), p, t ? t->t : scratch); }
     DP_REQUIRE(merkle_jobs_ok(jobs, verify_threads()), DP_ERR_VERIFY, "merkle path does not authenticate against the root");
   });
 }
@@ -1287,39 +1278,117 @@ int32_t dp_model_prove(dp_model* m, const int64_t* input, size_t ninput, uint64_
   });
 }
 }  // extern "C"
-// The body of dp_model_prove_batch and dp_model_prove_batch_ex: `nproofs` proofs with up to `concurrency` in flight. Proof k is that of input
-// at(k) = index ? index[k] : k — its words, its output row and its trace live at that number. `src` gives the trace of an input (by its number);
-// null: run_model on the input, on the thread that proves it or a helper (dp_model_prove_batch). Throws DpError.
+// ---- device inference and decode: the helpers of the entry points below
+static_assert(DP_INFER_OK == INFER_OK && DP_INFER_BAD_REQUANT == INFER_BAD_REQUANT && DP_INFER_BAD_TOKEN == INFER_BAD_TOKEN && DP_INFER_BAD_GELU == INFER_BAD_GELU &&
+              DP_INFER_BAD_LAYERNORM == INFER_BAD_LAYERNORM && DP_INFER_BAD_SOFTMAX == INFER_BAD_SOFTMAX && INFER_BAD_LAYERNORM_TABLE > DP_INFER_BAD_SOFTMAX && DP_INFER_ALL_KINDS == INFER_ALL_KINDS, "deep_prove_hip_infer.h and infer.h");
+// The program of a flag word, planned at its first use (flags 0: refuses LayerNorm / Softmax / Mha / GELU before any device work). `state` not null: its
+// constants on the device as well, made at the first call that has inputs — an empty call allocates nothing there.
+static InferProgram& infer_program_for(dp_model* m, uint32_t flags, InferDeviceState** state = nullptr) {
+  std::unique_ptr<InferProgram>& prog = m->infer_prog[flags];
+  if (!prog) prog.reset(new InferProgram(infer_plan(m->zk->model, flags)));
+  if (state) { if (!m->infer_state[flags]) m->infer_state[flags] = hip_infer_state_new(m->ctx->device_id); *state = m->infer_state[flags]; }
+  return *prog;
+}
+// reasons null: dp_model_infer_ex. Not null: dp_model_infer_checked (the same program and device constants for the same flag word)
+// rows not null: dp_model_infer_trace (the trace row of every input beside its outputs; row_cap words per row, *row_words = the words of one)
+static void model_infer_run(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, double* wall_ms,
+                            int64_t* rows, size_t row_cap, size_t* row_words) {
+  DP_REQUIRE(m && inputs && outputs && noutput, DP_ERR_ARG, "bad arguments");
+  DP_REQUIRE(!(flags & ~(uint32_t)DP_INFER_ALL_KINDS), DP_ERR_ARG, "dp_model_infer_ex: unknown flag bits");
+  DP_REQUIRE(ninput == m->zk->model.input_len, DP_ERR_SHAPE, "input length mismatch");
+  CtxLock lk(m->ctx);
+  const InferProgram& prog = infer_program_for(m, flags);
+  DP_REQUIRE(noutput_cap >= prog.output_len, DP_ERR_ARG, "output buffer too small");
+  *noutput = prog.output_len;
+  if (wall_ms) *wall_ms = 0;
+  if (rows) { DP_REQUIRE(row_words && row_cap >= prog.row_words, DP_ERR_ARG, "dp_model_infer_trace: row buffer too small"); *row_words = prog.row_words; }
+  if (!ninputs) return;
+  InferDeviceState* st = nullptr; infer_program_for(m, flags, &st);
+  hip_infer_run(m->ctx->dev, prog, st, inputs, ninputs, outputs, noutput_cap, wall_ms, reasons, rows, row_cap);
+}
+static int32_t model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, size_t* nrefused, double* wall_ms) {
+  return guard([&] {
+    if (nrefused) *nrefused = 0;
+    model_infer_run(m, inputs, ninputs, ninput, flags, outputs, noutput_cap, noutput, reasons, wall_ms, nullptr, 0, nullptr);
+    if (nrefused) for (size_t i = 0; i < ninputs; i++) *nrefused += reasons[i] != DP_INFER_OK;
+  });
+}
+// the model of a blob as dp_model_infer_host prepares it
+static ModelSpec host_model(const int64_t* model_blob, size_t nwords) {
+  ModelSpec m = parse_model(model_blob, nwords);
+  validate_model(m);
+  for (auto& l : m.layers) { prepare_fast_inference(l); if (l.kind == L_CONV) l.wfft = conv_weight_fft(l); }
+  return m;
+}
+// ---- decode (include/deep_prove_hip_decode.h): the semantics are decode_step's (infer.h), for the device loop and the host loop alike
+static_assert(DP_DECODE_STOP_EOS == DECODE_STOP_EOS && DP_DECODE_STOP_WINDOW == DECODE_STOP_WINDOW && DP_DECODE_STOP_MAX_NEW == DECODE_STOP_MAX_NEW && DP_DECODE_STOP_REFUSED == DECODE_STOP_REFUSED, "deep_prove_hip_decode.h and infer.h");
+// what the call itself can get wrong, for a model whose window and vocabulary are known
+static void decode_check_call(size_t seq, size_t vocab, const uint32_t* prompt_len, size_t nprompts, int64_t pad) {
+  DP_REQUIRE(pad >= 0 && (uint64_t)pad < vocab, DP_ERR_ARG, "dp_model_decode: pad " + std::to_string(pad) + " lies outside the vocabulary of " + std::to_string(vocab) + " tokens");
+  for (size_t i = 0; i < nprompts; i++)
+    DP_REQUIRE(prompt_len[i] >= 1 && prompt_len[i] <= seq, DP_ERR_ARG, "dp_model_decode: prompt_len " + std::to_string(prompt_len[i]) + " of prompt " + std::to_string(i) + " lies outside 1.." + std::to_string(seq));
+}
+// the class (DP_INFER_BAD_*) of a refusal of run_model, by the layer its message names; 0: not a refusal of the data
+static uint32_t decode_refusal_class(const DpError& e) {
+  if (e.code != DP_ERR_ARG) return DP_INFER_OK;
+  const std::string w = e.what();
+  static const std::pair<const char*, uint32_t> heads[] = {{"requant: value exceeds", DP_INFER_BAD_REQUANT}, {"embeddings: token outside", DP_INFER_BAD_TOKEN}, {"gelu: input out of range", DP_INFER_BAD_GELU},
+                                                           {"layernorm: input out of range", DP_INFER_BAD_LAYERNORM}, {"layernorm: the inverse square root", DP_INFER_BAD_LAYERNORM}, {"softmax: input out of range", DP_INFER_BAD_SOFTMAX}};
+  for (const auto& h : heads) if (w.rfind(h.first, 0) == 0) return h.second;
+  return DP_INFER_OK;
+}
+
+// ---- dp_model_prove_batch and dp_model_prove_batch_ex: one body, a sequence of steps. The policy — arena, cap, cohorts, launch groups, host threads — is
+// batch_plan.h's; the hand-over of inputs prepared ahead is prep_ahead.h's; what is left here is what touches the device and the model.
 using TraceSource = std::function<Trace(size_t)>;
-static void prove_batch_body(dp_model* m, const int64_t* inputs, size_t nproofs, size_t ninput, int32_t concurrency, const TraceSource* src, const size_t* index,
-                             uint64_t** proof_words, size_t* proof_nwords, int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms) {
-  {
-    DP_REQUIRE(m && inputs && proof_words && proof_nwords && nproofs > 0 && concurrency > 0 && concurrency <= 1024, DP_ERR_ARG, "bad arguments");
-    auto at = [index](size_t k) { return index ? index[k] : k; };
-    size_t nw = std::min<size_t>((size_t)concurrency, nproofs);
-    // worker 0 is the model's own context; the others get their own stream + arena on the same GPU and share the
-    // (read-only) model commitments
-    // Arena of a worker: DP_WORKER_ARENA_BYTES, else 1.25 x the largest footprint a proof of this model has had (one proof
-    // alone runs in latency mode, whose multi-workgroup sumchecks keep every fold level: an upper bound of what a proof in
-    // flight needs) + 64 MB (at least 256 MB), else — nothing proved yet — 1.5 GB. The number of proofs in flight is cut to what fits in
-    // 90 % of the free HBM instead of failing: `concurrency` is a cap, not a demand.
-    const char* env = getenv("DP_WORKER_ARENA_BYTES");
-    const size_t MB64 = size_t(64) << 20;
-    // (round 6: 1.125 x the footprint + 16 MB in steps of 16 MB — 336 MB for Dense-4M where 1.25 x + 64 MB in steps of 64 gave 448: a proof's footprint does not depend on
-    // its input, the margin only has to cover what latency mode and throughput mode allocate differently, and throughput mode allocates LESS; ~700 proofs fit in flight
-    // instead of ~540, and the rate still grows with them: 1 066 / 1 116 proofs/s at 448 / 660, tools/r06/call23.sh)
-    const size_t MB16 = size_t(16) << 20;
-    size_t arena = env ? strtoull(env, nullptr, 10) : m->prove_peak ? std::max(4 * MB64, ((m->prove_peak + m->prove_peak / 8 + MB16 + MB16 - 1) / MB16) * MB16) : (size_t(3) << 29);
+namespace {
+// The first error of a batch wins. fail(): from a proof worker — no further proof is handed out (next = nproofs); note(): after the proofs.
+struct FirstError {
+  std::atomic<size_t>& next; const size_t nproofs;
+  std::mutex mu; std::string msg; int code = 0;
+  FirstError(std::atomic<size_t>& next_, size_t nproofs_) : next(next_), nproofs(nproofs_) {}
+  void note(int c, const std::string& what) { std::lock_guard<std::mutex> g(mu); if (!code) { code = c; msg = what; } }
+  void fail(int c, const std::string& what) { note(c, what); next = nproofs; }
+  template <class F>
+  void guard_worker(F&& f) {
+    try { f(); }
+    catch (const DpError& e) { fail(e.code, e.what()); }
+    catch (const std::exception& e) { fail(DP_ERR_ARG, e.what()); }
+    catch (...) { fail(DP_ERR_ARG, "unknown exception in a proof worker"); }
+  }
+};
+// One call of prove_batch_body: `nproofs` proofs with up to `concurrency` in flight. Proof k is that of input at(k) = index ? index[k] : k — its words, its
+// output row and its trace live at that number. `src` gives the trace of an input (by its number); null: run_model on the input, on the thread that proves it
+// or a helper (dp_model_prove_batch).
+struct BatchRun {
+  dp_model* m; const int64_t* inputs; size_t nproofs, ninput; const TraceSource* src; const size_t* index;
+  uint64_t** proof_words; size_t* proof_nwords; int64_t* outputs; size_t noutput_cap; size_t* noutput;
+  const BatchEnv env = BatchEnv::read();
+  size_t arena = 0;
+  BatchPlan plan;
+  std::atomic<size_t> next{0};  // the proof handed out next
+  FirstError err{next, nproofs};
+  struct Prep { Trace tr; WitnessHost wh; };
+  std::unique_ptr<PrepAhead<Prep>> ahead;
+
+  size_t at(size_t k) const { return index ? index[k] : k; }
+  // worker 0 is the model's own context; the others get their own stream + arena on the same GPU and share the (read-only) model commitments
+  Dev& dev_of(size_t wi) { return wi == 0 ? *m->ctx->dev : *m->workers[wi - 1]; }
+  std::unique_ptr<Prep> make_prep(size_t i) {
+    std::unique_ptr<Prep> p(new Prep);
+    p->tr = src ? (*src)(at(i)) : run_model(m->zk->model, std::vector<int64_t>(inputs + at(i) * ninput, inputs + (at(i) + 1) * ninput));
+    p->wh = witness_host(*m->zk, p->tr);
+    return p;
+  }
+
+  // The workers `nw` proofs in flight need, as far as they fit; returns the proofs in flight there will be.
+  size_t ensure_workers(size_t nw) {
     if (m->workers.size() + 1 < nw) {
       // the cap is fixed by the first batch that needs more workers than exist (later batches must not creep into the reserve)
       if (!m->in_flight_cap) {
         size_t free_b = 0, total_b = 0; hip_mem_info(m->ctx->device_id, &free_b, &total_b);
-        const size_t per = arena + (size_t(24) << 20);  // + the worker's staging and small buffers (the twiddle / coset tables are the context's, shared)
-        // DP_HBM_FRACTION (default 0.9): the share of the FREE HBM this process sizes its workers against — less when several processes share one GPU
-        // (bench.py with DP_FORCE_DEVICE: both ranks read the same free figure at the same moment)
-        const double frac = getenv("DP_HBM_FRACTION") ? std::min(0.95, std::max(0.01, atof(getenv("DP_HBM_FRACTION")))) : 0.9;
-        m->in_flight_cap = m->workers.size() + 1 + (size_t)((double)free_b * frac / (double)per);
-        if (m->in_flight_cap < nw && getenv("DP_TIMING") && atoi(getenv("DP_TIMING"))) fprintf(stderr, "[dp timing] prove_batch: %zu proofs in flight asked, %zu fit in %.1f GB of free HBM (%.0f MB per worker)\n", nw, m->in_flight_cap, free_b / 1e9, per / 1048576.0);
+        m->in_flight_cap = in_flight_cap(m->workers.size(), free_b, arena, env);
+        if (m->in_flight_cap < nw && env.timing) fprintf(stderr, "[dp timing] prove_batch: %zu proofs in flight asked, %zu fit in %.1f GB of free HBM (%.0f MB per worker)\n", nw, m->in_flight_cap, free_b / 1e9, worker_hbm_bytes(arena) / 1048576.0);
       }
       nw = std::min(nw, m->in_flight_cap);
     }
@@ -1337,190 +1406,110 @@ static void prove_batch_body(dp_model* m, const int64_t* inputs, size_t nproofs,
       }
       share_pcs(w.get()); m->workers.push_back(std::move(w));
     }
-    m->last_in_flight = nw;
+    return nw;
+  }
+  // The plan's cohorts and launch groups on the model's cohort list, and the workers in their cohorts.
+  void assign_cohorts() {
     // several proofs in flight: throughput mode on every context (see hip_dev_set_latency_mode)
-    hip_dev_set_latency_mode(m->ctx->dev, nw == 1);
-    for (auto& w : m->workers) hip_dev_set_latency_mode(w.get(), nw == 1);
-    // Cohorts (hip_dev.hip struct Cohort, cohort.h): the proofs in flight are grouped into cohorts of DP_COHORT members (default: in flight / 22, rounded up)
-    // that prove in lock step — launch number i of all members of a cohort is ONE kernel launch — with one host thread per cohort.
-    // DP_COHORT=0: every proof on its own stream (the round-1 scheme).
-    const char* ce = getenv("DP_COHORT");
-    // Default: as many cohorts as hardware queues serve without time slicing (22 of the 24), each as small as that allows — a merged
-    // launch ends with its slowest member, so small cohorts stall less (batch of 8: 121 ms with cohorts of 1, 165 ms with one cohort
-    // of 8; batch of 64: 262 ms with cohorts of 3, 302 ms with 12; 256 in flight: cohorts of 12; profiles/r02_batch_cohort_sweep.txt)
-    size_t csize = ce ? (size_t)std::max(0, atoi(ce)) : std::max<size_t>(1, (nw + 22 - 1) / 22);
-    size_t nco = (csize >= 1 && nw > 1) ? (nw + csize - 1) / csize : 0;
-    while (m->cohorts.size() < nco) m->cohorts.push_back(hip_cohort_new());
-    // Launch groups (cohort.h): the cohorts are dealt round robin to DP_LAUNCH_GROUPS groups — default: the hardware queues of the process (GPU_MAX_HW_QUEUES, which
-    // the constructor above guarantees is present) when there are fewer of them than cohorts, otherwise one group per cohort, i.e. every cohort launches on
-    // its own as it always has. The cohorts of a group share one stream, one argument ring (the sum of theirs) and every launch: streams that share a hardware
-    // queue run their kernels one after the other, and a one-workgroup tail lasts as long as a member's dependent chain however many members it has — five or
-    // six cohorts on one queue pay it five or six times in a row, a group once. Host work stays where it was: one thread per cohort (cohorts of 176 on four
-    // threads are host-bound, NOTES_NEXT_ROUND.md). DP_STREAM_SHARE (cohorts taking turns on one stream, measured -3 % / -11 %,
-    // profiles/r05_stream_share_ab.txt) went with this: a group is the same sharing with the launches merged.
-    size_t ngroups = nco;
-    if (const char* ge = getenv("DP_LAUNCH_GROUPS")) ngroups = (size_t)std::max(1, atoi(ge));
-    else if (const char* qe = getenv("GPU_MAX_HW_QUEUES")) { const int nq = atoi(qe); if (nq >= 1 && (size_t)nq < nco) ngroups = (size_t)nq; }
-    ngroups = std::min(ngroups, nco);
-    for (size_t c = 0; c < nco; c++) {
-      if (c < ngroups) hip_cohort_lead(m->cohorts[c], (nco - c + ngroups - 1) / ngroups);  // cohorts c, c + ngroups, c + 2 ngroups, ...
-      else hip_cohort_follow(m->cohorts[c], m->cohorts[c % ngroups]);
+    hip_dev_set_latency_mode(m->ctx->dev, plan.nw == 1);
+    for (auto& w : m->workers) hip_dev_set_latency_mode(w.get(), plan.nw == 1);
+    while (m->cohorts.size() < plan.nco) m->cohorts.push_back(hip_cohort_new());
+    for (size_t c = 0; c < plan.nco; c++) {
+      if (c < plan.ngroups) hip_cohort_lead(m->cohorts[c], plan.lead(c));
+      else hip_cohort_follow(m->cohorts[c], m->cohorts[plan.leader_of(c)]);
     }
-    auto dev_of = [&](size_t wi) -> Dev& { return wi == 0 ? *m->ctx->dev : *m->workers[wi - 1]; };
-    std::atomic<size_t> next(0);
-    const bool timing = getenv("DP_TIMING") && atoi(getenv("DP_TIMING"));
-    std::mutex err_mu; std::string err; int err_code = 0;
-    for (size_t i = 0; i < nproofs; i++) { proof_words[at(i)] = nullptr; proof_nwords[at(i)] = 0; }
-    for (size_t wi = 0; wi < nw && nco; wi++) hip_dev_cohort_attach(&dev_of(wi), m->cohorts[wi % nco]);
-    // The host work a proof starts with — inference and the host half of the witness generation (zkml.h witness_host: lookup columns, table multiplicities;
-    // 0.6 ms for Dense-4M, ~10 ms for the transformer layer) — is made AHEAD of the proofs by DP_PREP_THREADS helper threads (default 2, 0 = off): the members of
-    // a cohort start a proof together on ONE host thread, and until the last of them has submitted its first launch the cohort's stream is idle.
-    // pst[i]: 0 nobody has touched input i, 1 being prepared, 2 ready in prep[i], 3 the helper failed (the worker repeats it so that the error is its own).
-    struct Prep { Trace tr; WitnessHost wh; };
-    std::vector<std::unique_ptr<Prep>> prep(nproofs);
-    std::unique_ptr<std::atomic<int>[]> pst(new std::atomic<int>[nproofs]);
-    for (size_t i = 0; i < nproofs; i++) pst[i].store(0, std::memory_order_relaxed);
-    auto make_prep = [&](size_t i) {
-      std::unique_ptr<Prep> p(new Prep);
-      p->tr = src ? (*src)(at(i)) : run_model(m->zk->model, std::vector<int64_t>(inputs + at(i) * ninput, inputs + (at(i) + 1) * ninput));
-      p->wh = witness_host(*m->zk, p->tr);
-      return p;
-    };
-    const char* pe = getenv("DP_PREP_THREADS");
-    const size_t nprep = nw > 1 ? (size_t)std::max(0, pe ? atoi(pe) : 2) : 0;
-    const size_t prep_ahead = getenv("DP_PREP_AHEAD") ? (size_t)std::max(1, atoi(getenv("DP_PREP_AHEAD"))) : nw;  // inputs prepared beyond the one handed out last
-    std::atomic<size_t> pnext(nw);  // (the first nw proofs start at once: their workers prepare them themselves)
-    std::atomic<bool> pstop(false);
-    auto prep_thread = [&] {
-      for (;;) {
-        const size_t i = pnext.fetch_add(1);
-        if (i >= nproofs) return;
-        while (!pstop.load(std::memory_order_relaxed) && i >= next.load(std::memory_order_relaxed) + prep_ahead) std::this_thread::sleep_for(std::chrono::microseconds(200));
-        if (pstop.load(std::memory_order_relaxed)) return;
-        if (i < next.load(std::memory_order_relaxed)) continue;  // handed out meanwhile (or the batch is being abandoned)
-        int e = 0;
-        if (!pst[i].compare_exchange_strong(e, 1)) continue;
-        try { prep[i] = make_prep(i); pst[i].store(2, std::memory_order_release); } catch (...) { pst[i].store(3, std::memory_order_release); }
-      }
-    };
-    // Serialising a finished proof (2.1 ms for the 5.9 MB of a Dense-4M proof) and copying it out used to run on the cohort's thread: the members of a cohort
-    // finish a proof together, so every pass of a cohort ended with members x 2.3 ms of host work during which its stream had nothing queued (48 ms of a 533 ms
-    // pass at 21 members). DP_SER_THREADS helper threads (default 2, 0 = inline) take it over; the batch returns when they have drained their queue.
-    // Measured (tools/r05/call20.sh, one box, alternating): WORSE — 483-512 against 679-694 proofs/s with two threads: the 14 proving threads spin on all the CPUs
-    // the process has, the helpers get their cycles late, and the last wave's 448 proofs queue behind two threads. Off by default; the faster serialiser
-    // (proof.h Writer: reserved once, bulk appends) is what shortens the stall instead.
-    const size_t nser = nw > 1 ? (size_t)std::max(0, getenv("DP_SER_THREADS") ? atoi(getenv("DP_SER_THREADS")) : 0) : 0;
-    std::mutex ser_mu; std::condition_variable ser_cv; std::deque<std::pair<size_t, Proof>> ser_q; bool ser_stop = false;
-    auto ser_thread = [&] {
-      for (;;) {
-        std::pair<size_t, Proof> job;
-        {
-          std::unique_lock<std::mutex> lk(ser_mu);
-          ser_cv.wait(lk, [&] { return ser_stop || !ser_q.empty(); });
-          if (ser_q.empty()) return;
-          job = std::move(ser_q.front()); ser_q.pop_front();
-        }
-        try { std::vector<u64> w = serialize_proof(job.second); proof_words[at(job.first)] = copy_out(w); proof_nwords[at(job.first)] = w.size(); }
-        catch (const std::exception& e) { std::lock_guard<std::mutex> g(err_mu); if (!err_code) { err_code = DP_ERR_OOM; err = std::string("serialising a proof: ") + e.what(); } }
-      }
-    };
-    auto t0 = std::chrono::steady_clock::now();
-    auto work = [&](size_t wi) {
-      Dev& dev = dev_of(wi);
-      try {
-        dev.bind_thread();
-        for (;;) {
-          size_t i = next.fetch_add(1);
-          if (i >= nproofs) break;
-          auto h0 = std::chrono::steady_clock::now();
-          std::unique_ptr<Prep> mine;
-          int e = 0;
-          if (pst[i].compare_exchange_strong(e, 1)) mine = make_prep(i);
-          else {
-            while ((e = pst[i].load(std::memory_order_acquire)) == 1) fiber_yield();
-            mine = e == 2 ? std::move(prep[i]) : make_prep(i);
-          }
-          Trace& tr = mine->tr;
-          auto h1 = std::chrono::steady_clock::now();
-          Transcript t = default_transcript();
-          Proof p = prove(*m->zk, dev, tr, t, &mine->wh);
-          auto h2 = std::chrono::steady_clock::now();
-          if (nser) {  // several proofs in flight: the finished proof goes to the serialiser threads, this fiber to its next proof (see `ser_thread`)
-            { std::lock_guard<std::mutex> g(ser_mu); ser_q.emplace_back(i, std::move(p)); }
-            ser_cv.notify_one();
-          } else { static thread_local std::vector<u64> ser_buf; serialize_proof_to(p, ser_buf); proof_words[at(i)] = copy_out(ser_buf); proof_nwords[at(i)] = ser_buf.size(); }
-          auto h3 = std::chrono::steady_clock::now();
-          if (timing && wi == 0) {
-            auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-            fprintf(stderr, "[dp timing] host phases of one proof: inference + witness columns (or the wait for the helper that made them) %.2f ms, prove %.2f ms (wall, shared thread), serialise %.2f ms, copy out %.2f ms\n", ms(h0, h1), ms(h1, h2), ms(h2, h3), ms(h3, std::chrono::steady_clock::now()));
-          }
-          if (outputs) { const std::vector<int64_t> o = model_output(m->zk->model, tr); DP_REQUIRE(o.size() <= noutput_cap, DP_ERR_ARG, "output buffer too small"); memcpy(outputs + at(i) * noutput_cap, o.data(), o.size() * 8); if (noutput) *noutput = o.size(); }
-        }
-      } catch (const DpError& e) { std::lock_guard<std::mutex> g(err_mu); if (!err_code) { err_code = e.code; err = e.what(); } next = nproofs; }
-      catch (const std::exception& e) { std::lock_guard<std::mutex> g(err_mu); if (!err_code) { err_code = DP_ERR_ARG; err = e.what(); } next = nproofs; }
-      catch (...) { std::lock_guard<std::mutex> g(err_mu); if (!err_code) { err_code = DP_ERR_ARG; err = "unknown exception in a proof worker"; } next = nproofs; }
-      // leaving the cohort releases the launches the other members have queued behind this one
-      if (nco) { try { hip_dev_cohort_detach(&dev); } catch (const std::exception& e) { std::lock_guard<std::mutex> g(err_mu); if (!err_code) { err_code = DP_ERR_HIP; err = e.what(); } next = nproofs; } }
-    };
-    // `nw` proofs in flight on `nth` host threads: every worker is a fiber; a thread switches to its next fiber whenever the
-    // current one waits for the device (fiber.h). All members of a cohort live on one thread (what several cohorts share is their launch group's, behind its lock);
-    // cohorts (or, without cohorts, workers) are dealt round robin to the threads. The thread count follows the CPUs the
-    // process may really use (cgroup quota), leaving two for the HIP runtime's own threads.
-    const char* te = getenv("DP_HOST_THREADS");
-    size_t nth = te ? (size_t)std::max(1, atoi(te)) : (size_t)std::max(1.0, host_cpu_budget() - 2.0);
-    if (!te && getenv("DP_HOST_SPONGE") && atoi(getenv("DP_HOST_SPONGE"))) {  // the sponge servers (csrc/sponge_host.h) spin too: they come out of the same CPU budget
-      const int S = getenv("DP_SPONGE_THREADS") ? std::max(1, atoi(getenv("DP_SPONGE_THREADS"))) : 6;
-      nth = (size_t)std::max(2.0, host_cpu_budget() - 2.0 - (double)S);
+    for (size_t wi = 0; wi < plan.nw && plan.nco; wi++) hip_dev_cohort_attach(&dev_of(wi), m->cohorts[plan.cohort_of(wi)]);
+  }
+  // proof i on worker wi: its trace and witness columns (made ahead, or here), the proof, its words and its output row at at(i)
+  void prove_one(size_t wi, Dev& dev, size_t i) {
+    auto h0 = std::chrono::steady_clock::now();
+    std::unique_ptr<Prep> mine = ahead->take(i, [this](size_t k) { return make_prep(k); }, fiber_yield);
+    Trace& tr = mine->tr;
+    auto h1 = std::chrono::steady_clock::now();
+    Transcript t = default_transcript();
+    Proof p = prove(*m->zk, dev, tr, t, &mine->wh);
+    auto h2 = std::chrono::steady_clock::now();
+    // (serialising on helper threads was measured worse, twice — DESIGN.md section 4; the faster serialiser, proof.h Writer, is what shortens the stall)
+    static thread_local std::vector<u64> ser_buf; serialize_proof_to(p, ser_buf); proof_words[at(i)] = copy_out(ser_buf); proof_nwords[at(i)] = ser_buf.size();
+    auto h3 = std::chrono::steady_clock::now();
+    if (env.timing && wi == 0) {
+      auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+      fprintf(stderr, "[dp timing] host phases of one proof: inference + witness columns (or the wait for the helper that made them) %.2f ms, prove %.2f ms (wall, shared thread), serialise %.2f ms, copy out %.2f ms\n", ms(h0, h1), ms(h1, h2), ms(h2, h3), ms(h3, std::chrono::steady_clock::now()));
     }
-    // with sleeping idle threads (fiber.h, DP_IDLE_SLEEP_US) a cohort's thread costs what its members' host work costs (~0.3 cores), not a whole core of polling:
-    // one thread per cohort as long as that is at most twice the CPU budget (22 cohorts on a 16-CPU quota: 6.3 cores busy)
-    if (!te && nco && nw > 1 && fiber_idle_sleep_ns() > 0 && (double)nco <= 2.0 * host_cpu_budget()) nth = std::max(nth, nco);
-    nth = std::min(nth, nco ? nco : nw);
-    // DP_COHORT_STAGGER_MS = d (diagnostic, default 0): cohort c starts c * d milliseconds late. The cohorts of a batch otherwise run IN PHASE — identical launch sequences
-    // from a common start: every queue in one-workgroup tails, then every queue in the streaming kernels, then every queue hashing (profiles/r06_timeline_704.txt). A
-    // staggered start persists (profiles/r06_timeline_704_staggered.txt) and changes the rate by nothing, in every combination tried (profiles/r06_plateau_sweeps.txt,
-    // call 16 / 20 / 21 / 24): a tail that starts beside other cohorts' hash layers waits milliseconds for room.
-    const double stagger_ms = getenv("DP_COHORT_STAGGER_MS") ? std::max(0.0, atof(getenv("DP_COHORT_STAGGER_MS"))) : 0.0;
-    auto run_thread = [&](size_t ti) {
-      if (nco && stagger_ms > 0 && nproofs > nw) std::this_thread::sleep_for(std::chrono::microseconds((long)((double)(ti % nco) * stagger_ms * 1000.0)));
-      FiberSched sched;
-      sched.idle_sleep = nw > 1;
-      for (size_t wi = 0; wi < nw; wi++) if ((nco ? wi % nco : wi) % nth == ti) fiber_spawn(sched, [&work, wi] { work(wi); });
-      fiber_run_all(sched);
-      for (auto& f : sched.fibers) if (f->failed) { std::lock_guard<std::mutex> g(err_mu); if (!err_code) { err_code = DP_ERR_ARG; err = "an exception escaped a proof worker's fiber"; } }
-    };
-    std::vector<std::thread> th, pth, sth;
+    if (outputs) { const std::vector<int64_t> o = model_output(m->zk->model, tr); DP_REQUIRE(o.size() <= noutput_cap, DP_ERR_ARG, "output buffer too small"); memcpy(outputs + at(i) * noutput_cap, o.data(), o.size() * 8); if (noutput) *noutput = o.size(); }
+  }
+  // the fiber of worker wi: proofs as long as there are any
+  void work(size_t wi) {
+    Dev& dev = dev_of(wi);
+    err.guard_worker([&] {
+      dev.bind_thread();
+      for (;;) {
+        const size_t i = next.fetch_add(1);
+        if (i >= nproofs) break;
+        prove_one(wi, dev, i);
+      }
+    });
+    // leaving the cohort releases the launches the other members have queued behind this one
+    if (plan.nco) { try { hip_dev_cohort_detach(&dev); } catch (const std::exception& e) { err.fail(DP_ERR_HIP, e.what()); } }
+  }
+  // host thread ti: the fibers of its workers, until all are finished
+  void run_thread(size_t ti) {
+    if (plan.stagger_ms > 0) std::this_thread::sleep_for(std::chrono::microseconds((long)((double)(ti % plan.nco) * plan.stagger_ms * 1000.0)));
+    FiberSched sched;
+    sched.idle_sleep = plan.nw > 1;
+    for (size_t wi = 0; wi < plan.nw; wi++) if (plan.thread_of(wi) == ti) fiber_spawn(sched, [this, wi] { work(wi); });
+    fiber_run_all(sched);
+    for (auto& f : sched.fibers) if (f->failed) err.note(DP_ERR_ARG, "an exception escaped a proof worker's fiber");
+  }
+  // every proof, on plan.nth host threads (thread 0 is the caller's) and plan.nprep helpers that prepare inputs ahead
+  void run_all() {
+    std::vector<std::thread> th, pth;
     // (threads this call spawns keep to the CPUs of the GPU's NUMA node, Dev::pin_thread; thread 0 is the caller's and keeps the affinity it came with)
     Dev* pin_dev = m->ctx->dev;
-    for (size_t k = 0; k < nser; k++) sth.emplace_back([&, pin_dev] { pin_dev->pin_thread(); ser_thread(); });
-    for (size_t k = 0; k < nprep && nproofs > nw; k++) pth.emplace_back([&, pin_dev] { pin_dev->pin_thread(); prep_thread(); });
-    for (size_t ti = 1; ti < nth; ti++) th.emplace_back([&, pin_dev, ti] { pin_dev->pin_thread(); run_thread(ti); });
+    for (size_t k = 0; k < plan.nprep; k++) pth.emplace_back([this, pin_dev] { pin_dev->pin_thread(); ahead->helper_loop(next, [this](size_t i) { return make_prep(i); }); });
+    for (size_t ti = 1; ti < plan.nth; ti++) th.emplace_back([this, pin_dev, ti] { pin_dev->pin_thread(); run_thread(ti); });
     run_thread(0);
     for (auto& t : th) t.join();
-    pstop.store(true);
+    ahead->stop();
     for (auto& t : pth) t.join();
-    { std::lock_guard<std::mutex> g(ser_mu); ser_stop = true; }
-    ser_cv.notify_all();
-    for (auto& t : sth) t.join();  // (they leave when the queue is empty: every proof is serialised and copied out)
-    for (size_t c = 0; c < ngroups; c++) { try { hip_cohort_drain(m->cohorts[c]); } catch (const std::exception& e) { if (!err_code) { err_code = DP_ERR_HIP; err = e.what(); } } }
-    if (nco && getenv("DP_TIMING") && atoi(getenv("DP_TIMING"))) {
-      size_t f = 0, p = 0; for (size_t c = 0; c < nco; c++) { size_t a, b; hip_cohort_stats(m->cohorts[c], &a, &b); f += a; p += b; }
+  }
+  // the launch groups drained, the DP_TIMING summary, the model's context back in latency mode; a failed batch hands out nothing and throws
+  void finish(std::chrono::steady_clock::time_point t0, double* wall_ms) {
+    for (size_t c = 0; c < plan.ngroups; c++) { try { hip_cohort_drain(m->cohorts[c]); } catch (const std::exception& e) { err.note(DP_ERR_HIP, e.what()); } }
+    if (plan.nco && env.timing) {
+      size_t f = 0, p = 0; for (size_t c = 0; c < plan.nco; c++) { size_t a, b; hip_cohort_stats(m->cohorts[c], &a, &b); f += a; p += b; }
       fprintf(stderr, "[dp timing] %zu cohorts of <= %zu proofs in %zu launch groups: %zu merged launches for %zu proof launches (%.0f merged launches per group, %.1f members per launch)\n",
-              nco, csize, ngroups, f, p, ngroups ? (double)f / (double)ngroups : 0.0, f ? (double)p / (double)f : 0.0);
+              plan.nco, plan.csize, plan.ngroups, f, p, plan.ngroups ? (double)f / (double)plan.ngroups : 0.0, f ? (double)p / (double)f : 0.0);
     }
-    if (getenv("DP_TIMING") && atoi(getenv("DP_TIMING"))) {
+    if (env.timing) {
       size_t wpeak = 0; for (auto& w : m->workers) wpeak = std::max(wpeak, hip_dev_arena_peak(w.get()));
-      fprintf(stderr, "[dp timing] prove_batch: %zu proofs, %zu in flight on %zu host threads, arena peak %.1f MB (context), %.1f MB (largest of the workers, arena %.1f MB each)\n", nproofs, nw, nth, hip_dev_arena_peak(m->ctx->dev) / 1048576.0, wpeak / 1048576.0, arena / 1048576.0);
+      fprintf(stderr, "[dp timing] prove_batch: %zu proofs, %zu in flight on %zu host threads, arena peak %.1f MB (context), %.1f MB (largest of the workers, arena %.1f MB each)\n", nproofs, plan.nw, plan.nth, hip_dev_arena_peak(m->ctx->dev) / 1048576.0, wpeak / 1048576.0, arena / 1048576.0);
     }
     if (wall_ms) *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     hip_dev_dump_sc_debug(m->ctx->dev); hip_dev_dump_host_stats(m->ctx->dev); hip_dump_wg_times();
-    for (size_t wi = 1; wi < nw && wi < 3; wi++) { hip_dev_dump_sc_debug(m->workers[wi - 1].get()); hip_dev_dump_host_stats(m->workers[wi - 1].get()); }
+    for (size_t wi = 1; wi < plan.nw && wi < 3; wi++) { hip_dev_dump_sc_debug(m->workers[wi - 1].get()); hip_dev_dump_host_stats(m->workers[wi - 1].get()); }
     hip_dev_set_latency_mode(m->ctx->dev, true);
-    if (err_code) { for (size_t i = 0; i < nproofs; i++) { dp_free(proof_words[at(i)]); proof_words[at(i)] = nullptr; proof_nwords[at(i)] = 0; } throw DpError(err_code, err); }
+    if (err.code) { for (size_t i = 0; i < nproofs; i++) { dp_free(proof_words[at(i)]); proof_words[at(i)] = nullptr; proof_nwords[at(i)] = 0; } throw DpError(err.code, err.msg); }
   }
+};
+}  // namespace
+// Throws DpError.
+static void prove_batch_body(dp_model* m, const int64_t* inputs, size_t nproofs, size_t ninput, int32_t concurrency, const TraceSource* src, const size_t* index,
+                             uint64_t** proof_words, size_t* proof_nwords, int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms) {
+  DP_REQUIRE(m && inputs && proof_words && proof_nwords && nproofs > 0 && concurrency > 0 && concurrency <= 1024, DP_ERR_ARG, "bad arguments");
+  BatchRun run{m, inputs, nproofs, ninput, src, index, proof_words, proof_nwords, outputs, noutput_cap, noutput};
+  run.arena = worker_arena_bytes(run.env, m->prove_peak);
+  const size_t nw = run.ensure_workers(std::min<size_t>((size_t)concurrency, nproofs));
+  m->last_in_flight = nw;
+  run.plan = plan_batch(run.env, nw, nproofs, host_cpu_budget(), fiber_idle_sleep_ns());
+  for (size_t i = 0; i < nproofs; i++) { proof_words[run.at(i)] = nullptr; proof_nwords[run.at(i)] = 0; }
+  run.assign_cohorts();
+  run.ahead.reset(new PrepAhead<BatchRun::Prep>(nproofs, nw, run.plan.prep_ahead));
+  const auto t0 = std::chrono::steady_clock::now();
+  run.run_all();
+  run.finish(t0, wall_ms);
 }
-static void model_infer_run(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, double* wall_ms,
-                            int64_t* rows, size_t row_cap, size_t* row_words);
+
 extern "C" {
 int32_t dp_model_prove_batch(dp_model* m, const int64_t* inputs, size_t nproofs, size_t ninput, int32_t concurrency,
                              uint64_t** proof_words, size_t* proof_nwords, int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms) {
@@ -1546,7 +1535,7 @@ int32_t dp_model_prove_batch_ex(dp_model* m, const int64_t* inputs, size_t nproo
     const char* mbs = getenv("DP_PROVE_TRACE_MB");
     const size_t budget = (size_t)((mbs && atof(mbs) > 0 ? std::min(atof(mbs), 1.0e9) : 4096.0) * 1048576.0);  // (a fraction of a megabyte is allowed)
     const size_t seg = std::min(nproofs, std::max<size_t>((size_t)concurrency, budget / (rw * 8)));
-    const bool timing = getenv("DP_TIMING") && atoi(getenv("DP_TIMING"));
+    const bool timing = timing_on();
     for (size_t i = 0; i < nproofs; i++) { proof_words[i] = nullptr; proof_nwords[i] = 0; }
     const auto t0 = std::chrono::steady_clock::now();
     std::unique_ptr<int64_t[]> rows(new int64_t[seg * rw]);  // (not zero-filled: the inference writes every row it hands on)
@@ -1583,9 +1572,7 @@ int32_t dp_model_prove_batch_ex(dp_model* m, const int64_t* inputs, size_t nproo
 int32_t dp_model_infer_host(const int64_t* model_blob, size_t nwords, const int64_t* input, size_t ninput, int64_t* output, size_t* noutput) {
   return guard([&] {
     DP_REQUIRE(model_blob && input && output && noutput, DP_ERR_ARG, "bad arguments");
-    ModelSpec m = parse_model(model_blob, nwords);
-    validate_model(m);
-    for (auto& l : m.layers) { prepare_fast_inference(l); if (l.kind == L_CONV) l.wfft = conv_weight_fft(l); }
+    const ModelSpec m = host_model(model_blob, nwords);
     Trace tr = run_model(m, std::vector<int64_t>(input, input + ninput));
     const std::vector<int64_t> o = model_output(m, tr);
     DP_REQUIRE(*noutput >= o.size(), DP_ERR_ARG, "output buffer too small");
@@ -1595,51 +1582,12 @@ int32_t dp_model_infer_host(const int64_t* model_blob, size_t nwords, const int6
 int32_t dp_model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, int64_t* outputs, size_t noutput_cap, size_t* noutput, double* wall_ms) {
   return dp_model_infer_ex(m, inputs, ninputs, ninput, 0, outputs, noutput_cap, noutput, wall_ms);
 }
-static_assert(DP_INFER_OK == INFER_OK && DP_INFER_BAD_REQUANT == INFER_BAD_REQUANT && DP_INFER_BAD_TOKEN == INFER_BAD_TOKEN && DP_INFER_BAD_GELU == INFER_BAD_GELU &&
-              DP_INFER_BAD_LAYERNORM == INFER_BAD_LAYERNORM && DP_INFER_BAD_SOFTMAX == INFER_BAD_SOFTMAX && INFER_BAD_LAYERNORM_TABLE > DP_INFER_BAD_SOFTMAX && DP_INFER_ALL_KINDS == INFER_ALL_KINDS, "deep_prove_hip_infer.h and infer.h");
-// reasons null: dp_model_infer_ex. Not null: dp_model_infer_checked (the same program and device constants for the same flag word)
-// rows not null: dp_model_infer_trace (the trace row of every input beside its outputs; row_cap words per row, *row_words = the words of one)
-}  // extern "C"
-static void model_infer_run(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, double* wall_ms,
-                            int64_t* rows, size_t row_cap, size_t* row_words) {
-  {
-    DP_REQUIRE(m && inputs && outputs && noutput, DP_ERR_ARG, "bad arguments");
-    DP_REQUIRE(!(flags & ~(uint32_t)DP_INFER_ALL_KINDS), DP_ERR_ARG, "dp_model_infer_ex: unknown flag bits");
-    const ModelSpec& spec = m->zk->model;
-    DP_REQUIRE(ninput == spec.input_len, DP_ERR_SHAPE, "input length mismatch");
-    CtxLock lk(m->ctx);
-    std::unique_ptr<InferProgram>& prog = m->infer_prog[flags];
-    if (!prog) prog.reset(new InferProgram(infer_plan(spec, flags)));  // (flags 0: refuses LayerNorm / Softmax / Mha / GELU before any device work)
-    DP_REQUIRE(noutput_cap >= prog->output_len, DP_ERR_ARG, "output buffer too small");
-    *noutput = prog->output_len;
-    if (wall_ms) *wall_ms = 0;
-    if (rows) { DP_REQUIRE(row_words && row_cap >= prog->row_words, DP_ERR_ARG, "dp_model_infer_trace: row buffer too small"); *row_words = prog->row_words; }
-    if (!ninputs) return;
-    if (!m->infer_state[flags]) m->infer_state[flags] = hip_infer_state_new(m->ctx->device_id);
-    hip_infer_run(m->ctx->dev, *prog, m->infer_state[flags], inputs, ninputs, outputs, noutput_cap, wall_ms, reasons, rows, row_cap);
-  }
-}
-extern "C" {
-static int32_t model_infer(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, size_t* nrefused, double* wall_ms) {
-  return guard([&] {
-    if (nrefused) *nrefused = 0;
-    model_infer_run(m, inputs, ninputs, ninput, flags, outputs, noutput_cap, noutput, reasons, wall_ms, nullptr, 0, nullptr);
-    if (nrefused) for (size_t i = 0; i < ninputs; i++) *nrefused += reasons[i] != DP_INFER_OK;
-  });
-}
 int32_t dp_model_infer_trace(dp_model* m, const int64_t* inputs, size_t ninputs, size_t ninput, uint32_t flags, int64_t* rows, size_t row_cap, size_t* row_words,
                              int64_t* outputs, size_t noutput_cap, size_t* noutput, uint32_t* reasons, double* wall_ms) {
   return guard([&] {
     DP_REQUIRE(rows && row_words, DP_ERR_ARG, "bad arguments");
     model_infer_run(m, inputs, ninputs, ninput, flags, outputs, noutput_cap, noutput, reasons, wall_ms, rows, row_cap, row_words);
   });
-}
-// the model of a blob as dp_model_infer_host prepares it
-static ModelSpec host_model(const int64_t* model_blob, size_t nwords) {
-  ModelSpec m = parse_model(model_blob, nwords);
-  validate_model(m);
-  for (auto& l : m.layers) { prepare_fast_inference(l); if (l.kind == L_CONV) l.wfft = conv_weight_fft(l); }
-  return m;
 }
 int32_t dp_model_trace_layout(const int64_t* model_blob, size_t nwords, uint64_t* entries, size_t cap_entries, size_t* nentries, size_t* row_words) {
   return guard([&] {
@@ -1670,39 +1618,20 @@ int32_t dp_model_infer_checked(dp_model* m, const int64_t* inputs, size_t ninput
   if (!reasons) return guard([] { throw DpError(DP_ERR_ARG, "bad arguments"); });
   return model_infer(m, inputs, ninputs, ninput, flags, outputs, noutput_cap, noutput, reasons, nrefused, wall_ms);
 }
-// ---- decode (include/deep_prove_hip_decode.h): the semantics are decode_step's (infer.h), for the device loop and the host loop alike
-static_assert(DP_DECODE_STOP_EOS == DECODE_STOP_EOS && DP_DECODE_STOP_WINDOW == DECODE_STOP_WINDOW && DP_DECODE_STOP_MAX_NEW == DECODE_STOP_MAX_NEW && DP_DECODE_STOP_REFUSED == DECODE_STOP_REFUSED, "deep_prove_hip_decode.h and infer.h");
-// what the call itself can get wrong, for a model whose window and vocabulary are known
-static void decode_check_call(size_t seq, size_t vocab, const uint32_t* prompt_len, size_t nprompts, int64_t pad) {
-  DP_REQUIRE(pad >= 0 && (uint64_t)pad < vocab, DP_ERR_ARG, "dp_model_decode: pad " + std::to_string(pad) + " lies outside the vocabulary of " + std::to_string(vocab) + " tokens");
-  for (size_t i = 0; i < nprompts; i++)
-    DP_REQUIRE(prompt_len[i] >= 1 && prompt_len[i] <= seq, DP_ERR_ARG, "dp_model_decode: prompt_len " + std::to_string(prompt_len[i]) + " of prompt " + std::to_string(i) + " lies outside 1.." + std::to_string(seq));
-}
-// the class (DP_INFER_BAD_*) of a refusal of run_model, by the layer its message names; 0: not a refusal of the data
-static uint32_t decode_refusal_class(const DpError& e) {
-  if (e.code != DP_ERR_ARG) return DP_INFER_OK;
-  const std::string w = e.what();
-  static const std::pair<const char*, uint32_t> heads[] = {{"requant: value exceeds", DP_INFER_BAD_REQUANT}, {"embeddings: token outside", DP_INFER_BAD_TOKEN}, {"gelu: input out of range", DP_INFER_BAD_GELU},
-                                                           {"layernorm: input out of range", DP_INFER_BAD_LAYERNORM}, {"layernorm: the inverse square root", DP_INFER_BAD_LAYERNORM}, {"softmax: input out of range", DP_INFER_BAD_SOFTMAX}};
-  for (const auto& h : heads) if (w.rfind(h.first, 0) == 0) return h.second;
-  return DP_INFER_OK;
-}
 int32_t dp_model_decode(dp_model* m, const int64_t* prompts, const uint32_t* prompt_len, size_t nprompts, uint32_t max_new, int64_t eos, int64_t pad, uint32_t flags,
                         int64_t* tokens, uint32_t* length, uint32_t* stop, uint32_t* reasons, int64_t* outputs, double* wall_ms) {
   return guard([&] {
     DP_REQUIRE(m && (!nprompts || (prompts && prompt_len && tokens && length && stop && reasons)), DP_ERR_ARG, "bad arguments");
     DP_REQUIRE(!(flags & ~(uint32_t)DP_INFER_ALL_KINDS), DP_ERR_ARG, "dp_model_decode: unknown flag bits");
-    const ModelSpec& spec = m->zk->model;
     size_t vocab = 0;
-    const size_t seq = decode_window(spec, &vocab);
+    const size_t seq = decode_window(m->zk->model, &vocab);
     decode_check_call(seq, vocab, prompt_len, nprompts, pad);
     CtxLock lk(m->ctx);
-    std::unique_ptr<InferProgram>& prog = m->infer_prog[flags];
-    if (!prog) prog.reset(new InferProgram(infer_plan(spec, flags)));  // (flags 0: refuses a GELU node before any device work)
+    const InferProgram& prog = infer_program_for(m, flags);  // (flags 0: refuses a GELU node before any device work)
     if (wall_ms) *wall_ms = 0;
     if (!nprompts) return;
-    if (!m->infer_state[flags]) m->infer_state[flags] = hip_infer_state_new(m->ctx->device_id);
-    hip_infer_decode(m->ctx->dev, *prog, m->infer_state[flags], prompts, prompt_len, nprompts, max_new, eos, pad, tokens, length, stop, reasons, outputs, wall_ms);
+    InferDeviceState* st = nullptr; infer_program_for(m, flags, &st);
+    hip_infer_decode(m->ctx->dev, prog, st, prompts, prompt_len, nprompts, max_new, eos, pad, tokens, length, stop, reasons, outputs, wall_ms);
   });
 }
 int32_t dp_model_decode_host(const int64_t* model_blob, size_t nwords, const int64_t* prompt, uint32_t prompt_len, uint32_t max_new, int64_t eos, int64_t pad,
@@ -1776,7 +1705,7 @@ int32_t dp_model_verifier_blob(const dp_model* m, uint64_t** words, size_t* nwor
 int32_t dp_verify(const uint64_t* vb, size_t vn, const uint64_t* pw, size_t pn, const int64_t* input, size_t ninput, const int64_t* output, size_t noutput) {
   return guard([&] {
     DP_REQUIRE(vb && pw && input && output, DP_ERR_ARG, "bad arguments");
-    const bool timing = getenv("DP_TIMING") && atoi(getenv("DP_TIMING"));
+    const bool timing = timing_on();
     auto t0 = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) { if (!timing) return; auto t1 = std::chrono::steady_clock::now(); fprintf(stderr, "[dp timing] dp_verify: %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count()); t0 = t1; };
     VerifierContext vc = vctx_from_words(vb, vn);
@@ -1786,9 +1715,7 @@ int32_t dp_verify(const uint64_t* vb, size_t vn, const uint64_t* pw, size_t pn, 
     Transcript t = default_transcript();
     // the Merkle paths are recorded while the protocol checks run and authenticated together afterwards (eight side by side on AVX-512 CPUs)
     std::vector<MerkleJob> jobs;
-    merkle_sink() = &jobs;
-    try { verify(vc, p, io, t); } catch (...) { merkle_sink() = nullptr; throw; }
-    merkle_sink() = nullptr;
+    { MerkleRecording rec(jobs); verify(vc, p, io, t); }
     lap("protocol checks");
     DP_REQUIRE(merkle_jobs_ok(jobs, verify_threads()), DP_ERR_VERIFY, "merkle path does not authenticate against the root");
     lap("merkle paths");
@@ -1804,8 +1731,7 @@ int32_t dp_verify_batch(dp_ctx* ctx, const uint64_t* vb, size_t vn, const uint64
     DP_REQUIRE(vb && proof_words && proof_nwords && inputs && outputs && results, DP_ERR_ARG, "bad arguments");
     auto t0 = std::chrono::steady_clock::now();
     const VerifierContext vc = vctx_from_words(vb, vn);
-    size_t nth = threads > 0 ? (size_t)threads : (size_t)std::max(1.0, host_cpu_budget() - 2.0);
-    nth = std::max<size_t>(1, std::min(nth, nproofs));
+    const size_t nth = std::max<size_t>(1, std::min(default_host_threads(threads, host_cpu_budget()), nproofs));
     std::atomic<size_t> next{0};
     auto work = [&]() {
       for (;;) {
@@ -1816,9 +1742,7 @@ int32_t dp_verify_batch(dp_ctx* ctx, const uint64_t* vb, size_t vn, const uint64
           Proof p = deserialize_proof(proof_words[i], proof_nwords[i]);
           IO io; io.input.assign(inputs + i * ninput, inputs + (i + 1) * ninput); io.output.assign(outputs + i * noutput, outputs + (i + 1) * noutput);
           Transcript t = default_transcript();
-          merkle_sink() = &jobs;
-          try { verify(vc, p, io, t); } catch (...) { merkle_sink() = nullptr; throw; }
-          merkle_sink() = nullptr;
+          { MerkleRecording rec(jobs); verify(vc, p, io, t); }
           // the recorded paths: one flat pool of sibling digests + per-path leaf digest, root, leaf-pair index, offset, depth
           const size_t n = jobs.size();
           size_t pool_n = 0; for (const MerkleJob& j : jobs) pool_n += j.depth;
@@ -1835,8 +1759,8 @@ int32_t dp_verify_batch(dp_ctx* ctx, const uint64_t* vb, size_t vn, const uint64
           if (ctx) { CtxLock lk(ctx); ok = ctx->dev->merkle_paths_check(leaf.data(), root.data(), x.data(), off.data(), depth.data(), n, pool.data(), pool_n, nullptr); }
           else ok = merkle_jobs_ok(jobs);
           results[i] = ok ? DP_OK : DP_ERR_VERIFY;
-        } catch (const DpError& e) { merkle_sink() = nullptr; results[i] = e.code == DP_ERR_VERIFY ? DP_ERR_VERIFY : DP_ERR_ARG; }
-        catch (const std::exception&) { merkle_sink() = nullptr; results[i] = DP_ERR_ARG; }
+        } catch (const DpError& e) { results[i] = e.code == DP_ERR_VERIFY ? DP_ERR_VERIFY : DP_ERR_ARG; }
+        catch (const std::exception&) { results[i] = DP_ERR_ARG; }
       }
     };
     std::vector<std::thread> th;

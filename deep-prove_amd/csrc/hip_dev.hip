@@ -7,6 +7,7 @@
 // are canonical u64, extension elements are 16-byte {c0,c1} pairs so one `global_load_dwordx4` per lane fetches one
 // element. A sumcheck pair (2b, 2b+1) is therefore 32 contiguous bytes per lane.
 #include "dev.h"
+#include "hip_host.h"
 #include "poseidon2_fast.h"
 #include "gl64_lazy.h"
 #include "sumcheck.h"

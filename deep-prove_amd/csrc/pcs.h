@@ -406,6 +406,13 @@ inline Digest host_leaf_pair_digest(bool is_ext, Ext l, Ext r) {  // hash_two_le
 // (Dev::merkle_paths_check: one path per lane); the paths point into the Proof object, which outlives the check.
 struct MerkleJob { Digest leaf; size_t x; const Digest* path; size_t depth; Digest root; };
 inline std::vector<MerkleJob>*& merkle_sink() { static thread_local std::vector<MerkleJob>* s = nullptr; return s; }
+// the calling thread records into `jobs` while this lives; the sink is cleared when the scope ends, by a throw as well
+struct MerkleRecording {
+  explicit MerkleRecording(std::vector<MerkleJob>& jobs) { merkle_sink() = &jobs; }
+  ~MerkleRecording() { merkle_sink() = nullptr; }
+  MerkleRecording(const MerkleRecording&) = delete;
+  MerkleRecording& operator=(const MerkleRecording&) = delete;
+};
 inline bool merkle_job_ok(const MerkleJob& j) {
   Digest h = j.leaf; size_t x = j.x;
   for (size_t l = 0; l < j.depth; l++) { h = (x & 1) ? host_compress(j.path[l], h) : host_compress(h, j.path[l]); x >>= 1; }
