@@ -2,8 +2,9 @@
 // The host flattens a ModelSpec into an InferProgram (infer_plan below: tensors, constants, one op per launch) once per model; hip_infer_run
 // (infer_kernels.inc, compiled into hip_dev.hip) executes it for a batch: activations are [batch][tensor], one launch serves the whole batch.
 // Which products take the i8 MFMA is decided here, statically: the weights within -128..127, K * 128 * 128 < 2^31 and the input produced by
-// a Requant (through ReLU / MaxPool / Flatten) or a model input the host has range-checked at upload. Everything else is 64-bit multiply-add
-// with the host's wrap-around.
+// a Requant (through ReLU / MaxPool / Flatten) or a model input the host has range-checked at upload. A convolution is such a product too
+// (k_infer_conv_i8, on the packed filter image of infer_conv_pack) when its padded kernel side is 4 or 8. Everything else is 64-bit
+// multiply-add with the host's wrap-around.
 // INFER_ALL_KINDS (dp_model_infer_ex, DP_INFER_ALL_KINDS) adds LayerNorm, Softmax, Mha and GELU. Their tables are constants of the model, made
 // here by the functions the prover uses (gelu_lut, inv_sqrt_lut, softmax_lut); on the device the three layers are integer work. The one float
 // computation that depends on the data, the shift of a Softmax row, stays on the host: at an IO_SOFTMAX hip_infer_run downloads the input of
@@ -35,6 +36,7 @@ enum InferQ { IQ_NO = 0, IQ_YES = 1, IQ_IF_INPUTS = 2 };  // every value of the 
 struct InferTensor { size_t len = 0; int q = IQ_NO; };
 // a constant of the model. h64 points into the ModelSpec (it lives as long as the dp_model); w8 = the same matrix as int8, transposed to [N][K]
 // (both operands of k_infer_gemm_i8 are read along K), empty when a weight does not fit. Uploaded at the first launch that reads it.
+// A conv's filter: w8 = its packed int8 image [kw][K] (infer_conv_pack below), the operand of k_infer_conv_i8, under the same rule.
 // A table (GELU, inverse square root, exponential) is made by the planner and lives in `own`.
 struct InferConst {
   const int64_t* h64 = nullptr; size_t n = 0; std::vector<int8_t> w8; std::vector<int64_t> own;
@@ -53,13 +55,21 @@ struct InferOp {
   int in0 = -1, in1 = -1, out = -1;  // tensors
   int w = -1, bias = -1;             // constants (IO_LAYERNORM: gamma, beta)
   int table = -1;                    // constant: the table of IO_GELU (rows -max .. max - 1), IO_LAYERNORM (rows -2^14 .. 2^14 - 1), IO_SOFTMAX (2^table bits rows)
-  InferGemmShape g;                  // IO_GEMM (B = constant w; the i8 form when in0 is q and w has an int8 copy), IO_GEMM2 (B = tensor in1)
+  InferGemmShape g;                  // IO_GEMM (B = constant w; the i8 form when in0 is q and w has an int8 copy), IO_GEMM2 (B = tensor in1); IO_CONV: g.K = the packed K of the int8 filter image
   int64_t left = 1, right = 1;       // IO_ADDC: left * x + right * w[i]; IO_ADD2: left * a + right * b; IO_REQUANT, IO_GELU, IO_LAYERNORM: left = multiplier; IO_SOFTMAX: left = scalar, right = bkm
   unsigned shift = 0, bits = 0;      // IO_REQUANT; IO_LAYERNORM: shift = range_check_bits; IO_SOFTMAX: bits = table bits
-  // IO_EMBED: vocabulary, embedding size; IO_MAXPOOL: c, h, w; IO_CONV: kw, kx, real_nw, nw, unp_out[3]; IO_GELU: max; IO_LAYERNORM: row length, N;
+  // IO_EMBED: vocabulary, embedding size; IO_MAXPOOL: c, h, w; IO_CONV: kw, kx, real_nw, nw, unp_out[3], ra (the filter rows of the int8 image; 0: none, the op stays on k_infer_conv); IO_GELU: max; IO_LAYERNORM: row length, N;
   // IO_SOFTMAX: C, R, K, zero chunks, zero vars (in1 = the shift buffer of the chunk, a tensor of C * R words per sample); IO_ARGMAX: rows, K
   size_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
+// k_infer_conv_i8 (infer_kernels.inc): a workgroup computes IC_TC output channels of a strip of IC_TP consecutive pixels of one sample's plane; the
+// filter tile goes through LDS in K slices of IC_TK bytes (row pitch IC_LDA). Its dynamic LDS, in this order: the filter slice, one word per
+// filter row of the packed K (where the row's input bytes start), and per input channel the span of int8 inputs the strip can touch —
+// IC_TP + (ra - 1) * nw + rn - 1 bytes, + 4 so that every fragment can be cut from whole aligned words, rounded up to 16
+constexpr unsigned IC_TC = 32, IC_TP = 128, IC_TK = 128, IC_LDA = IC_TK + 16, IC_LDS_MAX = 48 * 1024;
+DP_HD unsigned infer_conv_pitch(unsigned nw, unsigned ra, unsigned rn) { return (IC_TP + (ra - 1) * nw + rn + 3 + 15) & ~15u; }
+DP_HD unsigned infer_conv_tab_words(unsigned K, unsigned rn) { return (K / rn + 3) & ~3u; }
+DP_HD size_t infer_conv_lds(size_t kx, unsigned nw, unsigned ra, unsigned rn, unsigned K) { return (size_t)IC_TC * IC_LDA + 4 * (size_t)infer_conv_tab_words(K, rn) + kx * infer_conv_pitch(nw, ra, rn); }
 struct InferTap { int tensor = -1; size_t len = 0, off = 0; };  // words off .. off + len of a trace row are tensor `tensor`
 struct InferProgram {
   size_t input_len = 0, output_len = 0;
@@ -159,6 +169,29 @@ inline void infer_softmax_shifts(const LayerSpec& sm, const int64_t* x, size_t n
   for (size_t t = 1; t < nth; t++) th.emplace_back(part, t);
   part(0);
   for (std::thread& t : th) t.join();
+}
+// The int8 image of a conv's filter, the channel-side operand of k_infer_conv_i8. The filter is [kw][kx][rn][rn] (rn = real_nw, the padded
+// kernel side) and mostly padding: ra = the smallest number of leading filter rows that holds every non-zero weight of every filter of the
+// layer (at least 1). The image is [kw][K]: k = (j * ra + a) * rn + c for input channel j, filter row a < ra and column c < rn — c keeps the
+// padded rn, so rn consecutive k are rn consecutive input bytes —, zero padded from kx * ra * rn up to K, a multiple of the 32 of an MFMA
+// step. No image (w8 empty, ra = K = 0) unless rn is 4 or 8, nw a multiple of 4 (whole words of a plane are staged), every weight within
+// -128..127, K * 128 * 128 < 2^31 (the 32-bit accumulator is exact) and the kernel's LDS fits: the op then stays on k_infer_conv.
+struct InferConvImage { size_t ra = 0, K = 0; std::vector<int8_t> w8; };
+inline InferConvImage infer_conv_pack(const LayerSpec& l) {
+  InferConvImage im;
+  const size_t rn = l.real_nw, per = rn * rn, nf = l.kw * l.kx;
+  if ((rn != 4 && rn != 8) || l.nw % 4 || l.nw > 4096 || l.weights.size() != nf * per) return im;
+  size_t ra = 1;
+  for (size_t i = 0; i < nf * per; i++) {
+    if (l.weights[i] < -128 || l.weights[i] > 127) return im;
+    if (l.weights[i]) ra = std::max(ra, i % per / rn + 1);
+  }
+  const size_t K = (l.kx * ra * rn + 31) & ~size_t(31);
+  if (!((double)K * 128.0 * 128.0 < 2147483648.0) || infer_conv_lds(l.kx, (unsigned)l.nw, (unsigned)ra, (unsigned)rn, (unsigned)K) > IC_LDS_MAX) return im;
+  im.ra = ra; im.K = K; im.w8.assign(l.kw * K, 0);
+  for (size_t f = 0; f < nf; f++) for (size_t a = 0; a < ra; a++) for (size_t c = 0; c < rn; c++)
+    im.w8[f / l.kx * K + (f % l.kx * ra + a) * rn + c] = (int8_t)l.weights[(f * rn + a) * rn + c];
+  return im;
 }
 inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
   for (size_t id = 0; id < m.layers.size(); id++) {
@@ -300,6 +333,8 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
       DP_REQUIRE(alen == l.kx * l.nw * l.nw, DP_ERR_SHAPE, "conv: input size mismatch");
       o.kind = IO_CONV; o.w = new_const(l.weights.data(), l.weights.size()); o.bias = new_const(l.bias.data(), l.bias.size());
       o.d[0] = l.kw; o.d[1] = l.kx; o.d[2] = l.real_nw; o.d[3] = l.nw; o.d[4] = l.unp_out[0]; o.d[5] = l.unp_out[1]; o.d[6] = l.unp_out[2];
+      InferConvImage im = infer_conv_pack(l);
+      o.d[7] = im.ra; o.g.K = im.K; p.consts[(size_t)o.w].w8 = std::move(im.w8);
       o.out = new_tensor(l.kw * l.nw * l.nw, IQ_NO);
     } else if (l.kind == L_GELU) {
       const TableType tt = gelu_table(l);

@@ -160,6 +160,86 @@ __global__ __launch_bounds__(256) void k_infer_conv(const int64_t* __restrict__ 
   }
   o[i] = (int64_t)acc;
 }
+// The pixel-side fragment of k_infer_conv_i8: the lane's 16 consecutive k are 16 / RN filter rows of RN columns, and the RN inputs under row
+// q are RN consecutive bytes of the staged span, from byte 4 * (tab[q] + wl) + sh on (wl, sh: the lane's pixel of the strip, as a word and the
+// byte within it). They are cut from whole aligned LDS words with v_alignbyte_b32, whatever sh is
+template <int RN> __device__ __forceinline__ infer_v4i infer_conv_frag(const unsigned* xs, const unsigned* tab, unsigned q, unsigned wl, unsigned sh) {
+  infer_v4i v;
+#pragma unroll
+  for (int r = 0; r < 16 / RN; r++) {
+    const unsigned* w = xs + tab[q + r] + wl;
+    if (RN == 4) v[r] = (int)__builtin_amdgcn_alignbyte(w[1], w[0], sh);
+    else { const unsigned w1 = w[1]; v[2 * r] = (int)__builtin_amdgcn_alignbyte(w1, w[0], sh); v[2 * r + 1] = (int)__builtin_amdgcn_alignbyte(w[2], w1, sh); }
+  }
+  return v;
+}
+// k_infer_conv on the i8 MFMA, exact: out[b][ch][p] = bias[ch] + sum over (j, a, c) of x[b][j][p + a * nw + c] * f[ch][j][a][c] on the flat plane
+// index p < nn = nw * nw, then clear_garbage. x: the int8 copy of the input, [batch][kx][nn]; f: the packed filter image [kw][K] of
+// infer_conv_pack, k = (j * ra + a) * RN + c (RN = the padded kernel side, 4 or 8; K a multiple of 32 with K * 128 * 128 < 2^31).
+// A workgroup (4 waves) owns IC_TC = 32 output channels (blockIdx.y) of one strip of IC_TP = 128 consecutive pixels of one sample's plane
+// (blockIdx.x = sample * strips + strip: a strip never crosses a sample), a wave 32 channels x 32 pixels: one accumulator of
+// v_mfma_i32_32x32x32_i8 with the channels as its first operand and the pixels as its second, so that the D column — the lane — is the pixel and
+// every store of a register is 32 consecutive words of [b][ch][nn]. D row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
+// The im2col operand is never formed: the inputs of channel j the strip can touch are ONE span of the plane, IC_TP + (ra - 1) * nw + RN - 1
+// bytes from the strip's first pixel on. The kx spans are staged in LDS once (whole aligned words; words beyond the end of the plane are zeros
+// and are not read from memory: a term that leaves the plane is dropped, as in k_infer_conv), with a table of where the input bytes of every
+// filter row of the packed K start (rows of the K padding point at the first span: their weights are zero). The filter tile goes through LDS
+// in K slices of IC_TK = 128, zero beyond kw and K. Lane l of a wave holds 16 consecutive k (k0 + 16 * (l >> 5) ...) of channel l & 31 and of
+// pixel l & 31: both fragments follow the SAME (lane half, byte) -> k rule, byte t of the lane is k0 + 16 * (l >> 5) + t, so the products pair up
+// whatever order the instruction gives the 32 k of a step.
+// Every term that leaves the plane or wraps into the next row belongs to an output clear_garbage zeroes, so a workgroup whose channels are all
+// >= u0 or whose rows are all >= u1 stages nothing and stores zeros, and so does such a wave of a live workgroup. In bounds: sample < batch
+// (the grid), word reads of x below nn, 16-byte reads of f below row kw and column K, LDS reads within a span (infer_conv_pitch), stores at
+// ch < kw and p < nn.
+template <int RN> __global__ __launch_bounds__(256) void k_infer_conv_i8(const int8_t* __restrict__ x, const int8_t* __restrict__ f, const int64_t* __restrict__ bias, int64_t* __restrict__ o,
+                                                                          unsigned strips, unsigned kw, unsigned kx, unsigned ra, unsigned K, unsigned nw, unsigned u0, unsigned u1, unsigned u2) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ic_lds[];
+  int8_t* As = (int8_t*)ic_lds;
+  unsigned* tab = (unsigned*)(ic_lds + IC_TC * IC_LDA);
+  unsigned* xs = tab + infer_conv_tab_words(K, RN);
+  const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
+  const unsigned nn = nw * nw, pw = infer_conv_pitch(nw, ra, RN) / 4;  // (the pitch of a span in words)
+  const unsigned b = blockIdx.x / strips, p0 = (blockIdx.x % strips) * IC_TP, ch0 = blockIdx.y * IC_TC;
+  const unsigned pl = wave * 32 + l31, p = p0 + pl;
+  const bool tile_live = ch0 < u0 && p0 / nw < u1;                                         // (uniform in the workgroup)
+  const bool wave_live = tile_live && p0 + wave * 32 < nn && (p0 + wave * 32) / nw < u1;  // (uniform in the wave)
+  infer_v16i acc;
+#pragma unroll
+  for (int r = 0; r < 16; r++) acc[r] = 0;
+  if (tile_live) {
+    for (unsigned q = tid; q < K / RN; q += 256) tab[q] = q < kx * ra ? q / ra * pw + q % ra * (nw / 4) : 0;
+    for (unsigned i = tid; i < kx * pw; i += 256) {
+      const unsigned j = i / pw, at = p0 + 4 * (i % pw);
+      xs[i] = at < nn ? *(const unsigned*)(x + ((size_t)b * kx + j) * nn + at) : 0u;
+    }
+    const unsigned lr = tid >> 3, lc = (tid & 7) * 16;  // the 16 bytes of the filter slice this thread stages: tile row, byte column
+    for (unsigned k0 = 0; k0 < K; k0 += IC_TK) {
+      infer_v4i a = {0, 0, 0, 0};
+      if (ch0 + lr < kw && k0 + lc < K) a = *(const infer_v4i*)(f + (size_t)(ch0 + lr) * K + k0 + lc);
+      __syncthreads();  // (the fragments of the slice before have been read)
+      *(infer_v4i*)&As[lr * IC_LDA + lc] = a;
+      __syncthreads();  // (the first one: the spans and the table are in LDS, too)
+      if (wave_live) {
+#pragma unroll
+        for (unsigned s = 0; s < IC_TK / 32; s++) {
+          if (k0 + s * 32 < K) {
+            const infer_v4i fa = *(const infer_v4i*)&As[l31 * IC_LDA + s * 32 + half * 16];
+            const infer_v4i fb = infer_conv_frag<RN>(xs, tab, (k0 + s * 32 + half * 16) / RN, pl >> 2, pl & 3);
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa, fb, acc, 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+  if (p >= nn) return;
+  const bool keep = wave_live && p / nw < u1 && p % nw < u2;
+  int64_t* op = o + (size_t)b * kw * nn + p;
+#pragma unroll
+  for (int r = 0; r < 16; r++) {
+    const unsigned ch = ch0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+    if (ch < kw) op[(size_t)ch * nn] = keep && ch < u0 ? (int64_t)acc[r] + bias[ch] : (int64_t)0;
+  }
+}
 // Activation::Gelu (gelu_op): table[v * mult + max], the table's rows being -max .. max - 1. |v| > 2^20 or a scaled value outside the table
 // refuses the sample (per = words per sample) and nothing is read: the same test guards the table against the values of a sample refused earlier
 __global__ __launch_bounds__(256) void k_infer_gelu(const int64_t* __restrict__ x, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n, int64_t mult, int64_t mx,
@@ -364,7 +444,8 @@ static uint32_t infer_first_class(const uint32_t* hs, size_t nb) {
   return INFER_OK;
 }
 static dim3 infer_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
-// one op for the nb samples of the chunk: one launch. launches: by kind, [IO_KINDS + 2]: those of k_infer_gemm_i8
+// one op for the nb samples of the chunk: one launch. launches: by kind, [IO_KINDS + 2]: those of k_infer_gemm_i8, [IO_KINDS + 3]: those of
+// k_infer_conv_i8 (both are counted under their kind as well)
 static void infer_launch(const InferProgram& p, const InferOp& o, const InferScratch& m, InferDeviceState* st, hipStream_t s, size_t nb, size_t* launches) {
   static const bool no_mfma = getenv("DP_INFER_NO_MFMA") && atoi(getenv("DP_INFER_NO_MFMA"));
   auto c64 = [&](int c) { return infer_const64(p, st, c); };
@@ -385,7 +466,20 @@ static void infer_launch(const InferProgram& p, const InferOp& o, const InferScr
     case IO_ADD2: k_infer_add2<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.in1), m.T64(o.out), n, o.left, o.right); break;
     case IO_EMBED: k_infer_embed<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), m.T64(o.out), n, o.d[0], o.d[1], m.status(), len); break;
     case IO_MAXPOOL: k_infer_maxpool<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.out), m.T8(o.out), n, o.d[1], o.d[2]); break;
-    case IO_CONV: k_infer_conv<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), c64(o.bias), m.T64(o.out), n, o.d[0], o.d[1], o.d[2], o.d[3], o.d[4], o.d[5], o.d[6]); break;
+    case IO_CONV:
+      if (!no_mfma && m.q[(size_t)o.in0] && !p.consts[(size_t)o.w].w8.empty()) {  // (the planner made the image: rn is 4 or 8 and the LDS fits)
+        const unsigned kw = (unsigned)o.d[0], kx = (unsigned)o.d[1], rn = (unsigned)o.d[2], nw = (unsigned)o.d[3], ra = (unsigned)o.d[7], K = (unsigned)o.g.K;
+        const unsigned strips = (nw * nw + IC_TP - 1) / IC_TP;
+        const dim3 grid((unsigned)(nb * strips), (kw + IC_TC - 1) / IC_TC);
+        const size_t lds = infer_conv_lds(kx, nw, ra, rn, K);
+        DP_REQUIRE(nb * strips <= 0x7fffffffu, DP_ERR_ARG, "dp_model_infer: conv grid");
+        const int8_t* f8 = infer_const8(p, st, o.w);
+        const unsigned u0 = (unsigned)o.d[4], u1 = (unsigned)o.d[5], u2 = (unsigned)o.d[6];
+        if (rn == 4) k_infer_conv_i8<4><<<grid, 256, lds, s>>>(m.T8(o.in0), f8, c64(o.bias), m.T64(o.out), strips, kw, kx, ra, K, nw, u0, u1, u2);
+        else k_infer_conv_i8<8><<<grid, 256, lds, s>>>(m.T8(o.in0), f8, c64(o.bias), m.T64(o.out), strips, kw, kx, ra, K, nw, u0, u1, u2);
+        launches[IO_KINDS + 3]++;
+      } else k_infer_conv<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), c64(o.bias), m.T64(o.out), n, o.d[0], o.d[1], o.d[2], o.d[3], o.d[4], o.d[5], o.d[6]);
+      break;
     case IO_GELU: k_infer_gelu<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.table), m.T64(o.out), n, o.left, (int64_t)o.d[0], m.status(), len); break;
     case IO_LAYERNORM: {
       const size_t rows = n / o.d[0];
@@ -448,7 +542,7 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
   double tap_ms = 0;
   const size_t chunk = m.chunk, in_w = m.in_q ? 1 : 8;
   st->c64.resize(p.consts.size(), nullptr); st->c8.resize(p.consts.size(), nullptr);
-  size_t launches[IO_KINDS + 3] = {0}, nchunks = 0, trips = 0, nrefused = 0;
+  size_t launches[IO_KINDS + 4] = {0}, nchunks = 0, trips = 0, nrefused = 0;
   double trip_ms = 0;
   uint32_t stop = INFER_OK;  // plain mode (no `reasons`): the class of the refused sample that ends the call
   auto cleanup = [&] {
@@ -511,8 +605,8 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (wall_ms) *wall_ms = ms;
   const size_t n_i8 = launches[IO_KINDS + 2], n_i64 = launches[IO_GEMM] + launches[IO_GEMM2] - n_i8;
-  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu conv %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu argmax %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s%s\n",
-                   n_i8, n_i64, launches[IO_CONV], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], launches[IO_ARGMAX], trips, trip_ms,
+  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu conv %zu conv_i8 %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu argmax %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s%s\n",
+                   n_i8, n_i64, launches[IO_CONV], launches[IO_KINDS + 3], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], launches[IO_ARGMAX], trips, trip_ms,
                    ninputs, nchunks, chunk, (double)m.total / 1048576.0, m.in_q ? "int8" : "int64", ms,
                    taps ? ("; taps " + std::to_string(p.taps.size()) + " entries, " + std::to_string(p.row_words) + " words, pack_launches " + std::to_string(tap_launches) + " pack_ms " + std::to_string(tap_ms)).c_str() : "",
                    reasons ? ("; checked, refused " + std::to_string(nrefused)).c_str() : "");
@@ -546,7 +640,7 @@ void hip_infer_decode(Dev* d, const InferProgram& p, InferDeviceState* st, const
   const size_t tok_bytes = up(chunk * seq * 8), word_bytes = up(chunk * 4);
   char* dstate = nullptr; char* pin = nullptr;
   st->c64.resize(p.consts.size(), nullptr); st->c8.resize(p.consts.size(), nullptr);
-  size_t launches[IO_KINDS + 3] = {0}, nchunks = 0, nsteps = 0, nlaunch = 0, npolls = 0, trips = 0;
+  size_t launches[IO_KINDS + 4] = {0}, nchunks = 0, nsteps = 0, nlaunch = 0, npolls = 0, trips = 0;
   double trip_ms = 0, final_ms = 0;
   auto cleanup = [&] {
     (void)hipStreamSynchronize(s);
@@ -613,6 +707,6 @@ void hip_infer_decode(Dev* d, const InferProgram& p, InferDeviceState* st, const
   cleanup();
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (wall_ms) *wall_ms = ms;
-  for (size_t k = 0; k < IO_KINDS + 2; k++) nlaunch += launches[k];  // (launches[IO_KINDS + 2] counts the i8 form of launches counted under IO_GEMM)
+  for (size_t k = 0; k < IO_KINDS + 2; k++) nlaunch += launches[k];  // (launches[IO_KINDS + 2] and [IO_KINDS + 3] count the i8 forms of launches counted under IO_GEMM and IO_CONV)
   if (timing) fprintf(stderr, "[dp decode] prompts %zu chunks %zu steps %zu launches %zu polls %zu final_ms %.3f\n", nprompts, nchunks, nsteps, nlaunch, npolls, final_ms);
 }
