@@ -4,7 +4,9 @@
 // Which products take the i8 MFMA is decided here, statically: the weights within -128..127, K * 128 * 128 < 2^31 and the input produced by
 // a Requant (through ReLU / MaxPool / Flatten) or a model input the host has range-checked at upload. A convolution is such a product too
 // (k_infer_conv_i8, on the packed filter image of infer_conv_pack) when its padded kernel side is 4 or 8. Everything else is 64-bit
-// multiply-add with the host's wrap-around.
+// multiply-add with the host's wrap-around. The product of two tensors of the batch (IO_GEMM2: MatMul2, ConcatMatMul, the two products of an Mha node)
+// takes k_infer_gemm2_i8 when infer_gemm2_plan below finds a form for both operands and both have int8 copies; the left one may instead be a
+// two-plane tensor (IQ_PLANES: the probabilities a Softmax writes, when every entry of its table lies in 0..16383).
 // INFER_ALL_KINDS (dp_model_infer_ex, DP_INFER_ALL_KINDS) adds LayerNorm, Softmax, Mha and GELU. Their tables are constants of the model, made
 // here by the functions the prover uses (gelu_lut, inv_sqrt_lut, softmax_lut); on the device the three layers are integer work. The one float
 // computation that depends on the data, the shift of a Softmax row, stays on the host: at an IO_SOFTMAX hip_infer_run downloads the input of
@@ -32,8 +34,12 @@
 
 namespace dp {
 
-enum InferQ { IQ_NO = 0, IQ_YES = 1, IQ_IF_INPUTS = 2 };  // every value of the tensor within -128..127: never / always / iff the model inputs of the call are
+// every value of the tensor within -128..127: never / always / iff the model inputs of the call are; IQ_PLANES: every value within 0..16383, the
+// tensor has two int8 planes (lo = v & 127, hi = v >> 7) and NO int8 copy — only the left operand of k_infer_gemm2_i8 reads them
+enum InferQ { IQ_NO = 0, IQ_YES = 1, IQ_IF_INPUTS = 2, IQ_PLANES = 3 };
 struct InferTensor { size_t len = 0; int q = IQ_NO; };
+// what ReLU / MaxPool make of their input's form: they keep -128..127 and write the int8 copy themselves; they write no planes
+inline int infer_q_through(int q) { return q == IQ_PLANES ? (int)IQ_NO : q; }
 // a constant of the model. h64 points into the ModelSpec (it lives as long as the dp_model); w8 = the same matrix as int8, transposed to [N][K]
 // (both operands of k_infer_gemm_i8 are read along K), empty when a weight does not fit. Uploaded at the first launch that reads it.
 // A conv's filter: w8 = its packed int8 image [kw][K] (infer_conv_pack below), the operand of k_infer_conv_i8, under the same rule.
@@ -59,7 +65,8 @@ struct InferOp {
   int64_t left = 1, right = 1;       // IO_ADDC: left * x + right * w[i]; IO_ADD2: left * a + right * b; IO_REQUANT, IO_GELU, IO_LAYERNORM: left = multiplier; IO_SOFTMAX: left = scalar, right = bkm
   unsigned shift = 0, bits = 0;      // IO_REQUANT; IO_LAYERNORM: shift = range_check_bits; IO_SOFTMAX: bits = table bits
   // IO_EMBED: vocabulary, embedding size; IO_MAXPOOL: c, h, w; IO_CONV: kw, kx, real_nw, nw, unp_out[3], ra (the filter rows of the int8 image; 0: none, the op stays on k_infer_conv); IO_GELU: max; IO_LAYERNORM: row length, N;
-  // IO_SOFTMAX: C, R, K, zero chunks, zero vars (in1 = the shift buffer of the chunk, a tensor of C * R words per sample); IO_ARGMAX: rows, K
+  // IO_SOFTMAX: C, R, K, zero chunks, zero vars (in1 = the shift buffer of the chunk, a tensor of C * R words per sample); IO_ARGMAX: rows, K;
+  // IO_GEMM2: d[0] = infer_gemm2_plan (IG2_*; 0: the op stays on k_infer_gemm_i64)
   size_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 // k_infer_conv_i8 (infer_kernels.inc): a workgroup computes IC_TC output channels of a strip of IC_TP consecutive pixels of one sample's plane; the
@@ -70,6 +77,24 @@ constexpr unsigned IC_TC = 32, IC_TP = 128, IC_TK = 128, IC_LDA = IC_TK + 16, IC
 DP_HD unsigned infer_conv_pitch(unsigned nw, unsigned ra, unsigned rn) { return (IC_TP + (ra - 1) * nw + rn + 3 + 15) & ~15u; }
 DP_HD unsigned infer_conv_tab_words(unsigned K, unsigned rn) { return (K / rn + 3) & ~3u; }
 DP_HD size_t infer_conv_lds(size_t kx, unsigned nw, unsigned ra, unsigned rn, unsigned K) { return (size_t)IC_TC * IC_LDA + 4 * (size_t)infer_conv_tab_words(K, rn) + kx * infer_conv_pitch(nw, ra, rn); }
+// The static half of "does this IO_GEMM2 take k_infer_gemm2_i8" (the other half, at the launch: both tensors have their int8 form in this call).
+// Each operand needs a unit stride along m (IG2_*K: staged with loads along K) or along its other matrix axis, r for A / n for B (IG2_*T: read along
+// that axis and transposed on the way into LDS); one whose unit stride is the concat axis is not served. K * 128 * 128 < 2^31 keeps the 32-bit
+// accumulator exact (the rule of weight_const). IG2_*W: the wide loads of the form — 16 bytes along K, 4 bytes along r / n — are aligned for every
+// (sample, concat index, row) and never leave the matrix: the int8 copy of a tensor starts 256-aligned, so the per-sample length, the concat and
+// row strides and the extent along the load must all be multiples of the load. lenA / lenB: the words of a sample of the two tensors.
+constexpr unsigned IG2_OK = 1, IG2_AT = 2, IG2_BT = 4, IG2_AW = 8, IG2_BW = 16;
+inline unsigned infer_gemm2_plan(const InferGemmShape& g, size_t lenA, size_t lenB) {
+  if (!g.C || !g.R || !g.K || !g.N || !((double)g.K * 128.0 * 128.0 < 2147483648.0)) return 0;
+  auto form = [&](size_t sK, size_t sX, size_t sC, size_t X, size_t len, unsigned T, unsigned W) -> int {
+    const bool t = sK != 1;
+    if (t && sX != 1) return -1;
+    const size_t w = t ? 4 : 16, along = t ? X : g.K, across = t ? sK : sX;
+    return (int)((t ? T : 0) | (along % w == 0 && across % w == 0 && (g.C == 1 || sC % w == 0) && len % w == 0 ? W : 0));
+  };
+  const int a = form(g.sAm, g.sAr, g.sAc, g.R, lenA, IG2_AT, IG2_AW), b = form(g.sBm, g.sBn, g.sBc, g.N, lenB, IG2_BT, IG2_BW);
+  return a < 0 || b < 0 ? 0 : IG2_OK | (unsigned)a | (unsigned)b;
+}
 struct InferTap { int tensor = -1; size_t len = 0, off = 0; };  // words off .. off + len of a trace row are tensor `tensor`
 struct InferProgram {
   size_t input_len = 0, output_len = 0;
@@ -255,6 +280,7 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
     size_t so[3] = {g.R * g.N, g.N, 1};
     if (!l.cm_perm.empty()) { const size_t st[3] = {g.out[1] * g.out[2], g.out[2], 1}; for (int d = 0; d < 3; d++) so[l.cm_perm[d]] = st[d]; }
     o.g.sOc = so[0]; o.g.sOr = so[1]; o.g.sOn = so[2];
+    o.d[0] = infer_gemm2_plan(o.g, p.tensors[(size_t)a].len, p.tensors[(size_t)b].len);
     o.out = new_tensor(o.g.C * o.g.R * o.g.N, IQ_NO);
     p.ops.push_back(o);
     return o.out;
@@ -266,7 +292,9 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
     InferOp o; o.kind = IO_SOFTMAX; o.node = (int)id; o.in0 = a; o.in1 = new_tensor(C * R, IQ_NO);
     o.table = table_const(softmax_table(l)); o.left = l.sm_scalar; o.right = l.sm_bkm; o.bits = l.sm_table_size;
     o.d[0] = C; o.d[1] = R; o.d[2] = K; o.d[3] = l.sm_zero_chunks; o.d[4] = l.sm_zero_vars;
-    o.out = new_tensor(C * R * K, IQ_NO);
+    // the output is an entry of the table or zero, whatever the data (the index is masked): two planes when every entry fits them
+    const std::vector<int64_t>& tab = p.consts[(size_t)o.table].own;
+    o.out = new_tensor(C * R * K, std::all_of(tab.begin(), tab.end(), [](int64_t v) { return v >= 0 && v <= 16383; }) ? IQ_PLANES : IQ_NO);
     p.ops.push_back(o);
     return o.out;
   };
@@ -308,6 +336,7 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
       DP_REQUIRE(l.nrows && alen % l.nrows == 0 && blen == l.nrows * l.ncols, DP_ERR_SHAPE, "matmul2: input shapes");
       o.g.C = 1; o.g.R = alen / l.nrows; o.g.K = l.nrows; o.g.N = l.ncols; o.g.sAr = l.nrows; o.g.sAm = 1;
       o.g.sBm = l.mm_transpose ? 1 : l.ncols; o.g.sBn = l.mm_transpose ? l.nrows : 1; o.g.sOr = l.ncols; o.g.sOn = 1;
+      o.d[0] = infer_gemm2_plan(o.g, alen, blen);
       o.out = new_tensor(o.g.C * o.g.R * o.g.N, IQ_NO);
       p.ops.push_back(o); slot[id] = {o.out};
       continue;
@@ -315,7 +344,7 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
     if (l.kind == L_REQUANT) {
       o.kind = IO_REQUANT; o.left = l.fixed_point_multiplier; o.shift = l.shift(); o.bits = l.intermediate_bit_size;
       o.out = new_tensor(alen, IQ_YES);
-    } else if (l.kind == L_RELU) { o.kind = IO_RELU; o.out = new_tensor(alen, p.tensors[(size_t)a].q); }
+    } else if (l.kind == L_RELU) { o.kind = IO_RELU; o.out = new_tensor(alen, infer_q_through(p.tensors[(size_t)a].q)); }
     else if (l.kind == L_ADD || l.kind == L_POSITIONAL) {
       if (l.kind == L_ADD) DP_REQUIRE(alen == l.weights.size(), DP_ERR_SHAPE, "add: operand size mismatch");
       else DP_REQUIRE(l.ncols && alen % l.ncols == 0 && alen <= l.weights.size(), DP_ERR_SHAPE, "positional: input shape");
@@ -328,7 +357,7 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
       o.kind = IO_EMBED; o.w = new_const(l.weights.data(), l.nrows * l.ncols); o.d[0] = l.nrows; o.d[1] = l.ncols; o.out = new_tensor(alen * l.ncols, IQ_NO);
     } else if (l.kind == L_MAXPOOL) {
       DP_REQUIRE(alen == l.pin[0] * l.pin[1] * l.pin[2], DP_ERR_SHAPE, "maxpool: input size mismatch");
-      o.kind = IO_MAXPOOL; o.d[0] = l.pin[0]; o.d[1] = l.pin[1]; o.d[2] = l.pin[2]; o.out = new_tensor(alen / 4, p.tensors[(size_t)a].q);
+      o.kind = IO_MAXPOOL; o.d[0] = l.pin[0]; o.d[1] = l.pin[1]; o.d[2] = l.pin[2]; o.out = new_tensor(alen / 4, infer_q_through(p.tensors[(size_t)a].q));
     } else if (l.kind == L_CONV) {
       DP_REQUIRE(alen == l.kx * l.nw * l.nw, DP_ERR_SHAPE, "conv: input size mismatch");
       o.kind = IO_CONV; o.w = new_const(l.weights.data(), l.weights.size()); o.bias = new_const(l.bias.data(), l.bias.size());

@@ -1,6 +1,7 @@
 // Kernels and the batch runner of dp_model_infer (infer.h). Included by hip_dev.hip after HipDev; not part of kernels.inc (the SIMT-emulator
 // build of tests/ cuts its kernels from there). Activations are [batch][tensor] int64, with an int8 copy next to every tensor whose values are
-// known to lie within -128..127 (what a Requant writes, and what ReLU / MaxPool make of it): the int8 copies are the operands of k_infer_gemm_i8.
+// known to lie within -128..127 (what a Requant writes, and what ReLU / MaxPool make of it): the int8 copies are the operands of k_infer_gemm_i8,
+// k_infer_conv_i8 and k_infer_gemm2_i8. The probabilities of a Softmax (0..4096) have two int8 planes instead, the left operand of k_infer_gemm2_i8.
 // Bad data (a Requant input beyond its bit size, a token outside the vocabulary, ...) refuses its sample: the chunk has one status word per
 // sample, which the five kernels that can refuse data set with a vector atomic to the class (INFER_BAD_* of infer.h) of the first op that refused
 // the sample; the host reads the words with the outputs. Ops run in stream order and the word only ever goes from zero to a class
@@ -91,6 +92,102 @@ __global__ __launch_bounds__(256) void k_infer_gemm_i64(const int64_t* __restric
   for (size_t k = 0; k < g.K; k++) acc += (uint64_t)a[k * g.sAm] * (uint64_t)w[k * g.sBm];
   if (bias) acc += (uint64_t)bias[n];
   O[b * lenO + c * g.sOc + r * g.sOr + n * g.sOn] = (int64_t)acc;
+}
+// One thread's 16 bytes of a 64 x IG_TK operand slice of k_infer_gemm2_i8, as they will lie in LDS ([tile row][k], k contiguous). X: the int8
+// matrix of one (sample, concat index), element (row, k) at X[row * sRow + k * sK] for row < rows and k < K; exactly one of the strides is 1.
+// sK == 1: thread t holds k0 + 16 * (t & 3) ... + 15 of tile row t >> 2 — one 16-byte load when `wide`, else byte by byte.
+// sRow == 1: thread t reads rows 4 * (t & 15) ... + 3 (one word when `wide`, else byte by byte) at each of k0 + 4 * (t >> 4) ... + 3, along the
+// contiguous axis, and transposes the 4 x 4 bytes in registers: word i of the result is row 4 * (t & 15) + i, bytes k ... k + 3.
+// Rows and k beyond the matrix are zeros and are not read; `wide` (infer_gemm2_plan) says the load is aligned and inside the matrix whenever its
+// first byte is.
+__device__ __forceinline__ infer_v4i infer_g2_load(const int8_t* __restrict__ X, size_t rows, size_t K, size_t sRow, size_t sK, size_t row0, size_t k0, bool wide, int tid) {
+  infer_v4i v = {0, 0, 0, 0};
+  if (sK == 1) {
+    const size_t row = row0 + (size_t)(tid >> 2), k = k0 + (size_t)(tid & 3) * 16;
+    if (row >= rows || k >= K) return v;
+    const int8_t* p = X + row * sRow + k;
+    if (wide) return *(const infer_v4i*)p;
+    unsigned w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 16; j++) if (k + j < K) w[j >> 2] |= (unsigned)(uint8_t)p[j] << (8 * (j & 3));
+    v[0] = (int)w[0]; v[1] = (int)w[1]; v[2] = (int)w[2]; v[3] = (int)w[3];
+    return v;
+  }
+  const size_t row = row0 + (size_t)(tid & 15) * 4, k = k0 + (size_t)(tid >> 4) * 4;
+  if (row >= rows) return v;
+  unsigned w[4] = {0, 0, 0, 0};  // w[j]: rows row ... row + 3 at k + j
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    if (k + j >= K) continue;
+    const int8_t* p = X + (k + j) * sK + row;
+    if (wide) w[j] = *(const unsigned*)p;
+    else for (int i = 0; i < 4; i++) if (row + i < rows) w[j] |= (unsigned)(uint8_t)p[i] << (8 * i);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) v[i] = (int)(((w[0] >> (8 * i)) & 0xffu) | (((w[1] >> (8 * i)) & 0xffu) << 8) | (((w[2] >> (8 * i)) & 0xffu) << 16) | (((w[3] >> (8 * i)) & 0xffu) << 24));
+  return v;
+}
+__device__ __forceinline__ void infer_g2_store(int8_t* S, infer_v4i v, bool k_major, int tid) {
+  if (k_major) { *(infer_v4i*)&S[(tid >> 2) * IG_LD + (tid & 3) * 16] = v; return; }
+#pragma unroll
+  for (int i = 0; i < 4; i++) *(int*)&S[((tid & 15) * 4 + i) * IG_LD + (tid >> 4) * 4] = v[i];
+}
+// The product of two tensors of the batch on the i8 MFMA (IO_GEMM2: MatMul2, ConcatMatMul, Q K^T and probabilities x V of an Mha node), exact:
+// out[b][c*sOc + r*sOr + n*sOn] = sum_m A[b][c*sAc + r*sAr + m*sAm] * B[b][c*sBc + m*sBm + n*sBn], A and B the int8 copies of the two tensors
+// (lenA, lenB, lenO: words per sample), accumulated in 32 bits (infer_gemm2_plan has checked K * 128 * 128 < 2^31) and stored as int64 at any
+// output strides. The problems are many and small, so a workgroup (4 waves, one 32 x 32 accumulator each) owns one IG_TM x IG_TN tile of ONE
+// (sample, concat index): blockIdx.x = ((b * C + c) * tiles of R + tile of r) * tiles of N + tile of n, and a tile never crosses either. Each
+// operand goes through LDS as [tile row][k] in K slices of IG_TK, whatever its layout in memory: infer_g2_load reads along the operand's
+// contiguous axis (m, or r / n with a 4 x 4 byte transposition in registers) and zero-fills beyond R, N and K in registers, nothing is read past
+// a matrix. Fragments are then 16 aligned bytes along k, and lane l holds k 16 * (l >> 5) ... of row l & 31 of A and of column l & 31 of B: both
+// follow the SAME (lane half, byte) -> k rule, as in k_infer_gemm_i8. D: column = l & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (l >> 5).
+// PL: A is a two-plane tensor (values 0..16383: A = lo, A2 = hi = v >> 7, both 0..127): two accumulators over the same B fragment, the result
+// (int64)acc_hi * 128 + acc_lo; each plane keeps the accumulator bound. A wave whose 32 x 32 block lies outside R x N multiplies and stores nothing.
+template <bool PL> __global__ __launch_bounds__(256) void k_infer_gemm2_i8(const int8_t* __restrict__ A, const int8_t* __restrict__ A2, size_t lenA, const int8_t* __restrict__ B, size_t lenB,
+                                                                           int64_t* __restrict__ O, size_t lenO, InferGemmShape g, unsigned tr, unsigned tn, unsigned flags) {
+  __shared__ __attribute__((aligned(16))) int8_t As[(PL ? 2 : 1) * IG_TM * IG_LD];
+  __shared__ __attribute__((aligned(16))) int8_t Bs[IG_TN * IG_LD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned t = blockIdx.x;
+  const size_t n0 = (size_t)(t % tn) * IG_TN; t /= tn;
+  const size_t r0 = (size_t)(t % tr) * IG_TM; t /= tr;
+  const size_t c = t % (unsigned)g.C, b = t / (unsigned)g.C;
+  const size_t offA = b * lenA + c * g.sAc;
+  const int8_t* Bm = B + b * lenB + c * g.sBc;
+  const bool a_k = !(flags & IG2_AT), b_k = !(flags & IG2_BT), a_w = flags & IG2_AW, b_w = flags & IG2_BW;
+  const size_t sAr = a_k ? g.sAr : 1, sAm = a_k ? 1 : g.sAm, sBn = b_k ? g.sBn : 1, sBm = b_k ? 1 : g.sBm;  // (the unit stride as a constant)
+  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
+  const bool live = r0 + wm < g.R && n0 + wn < g.N;  // (uniform in the wave)
+  infer_v16i acc, acc2;
+#pragma unroll
+  for (int r = 0; r < 16; r++) acc[r] = acc2[r] = 0;
+  for (size_t k0 = 0; k0 < g.K; k0 += IG_TK) {
+    const infer_v4i a = infer_g2_load(A + offA, g.R, g.K, sAr, sAm, r0, k0, a_w, tid), bb = infer_g2_load(Bm, g.N, g.K, sBn, sBm, n0, k0, b_w, tid);
+    infer_v4i a2 = {0, 0, 0, 0};
+    if (PL) a2 = infer_g2_load(A2 + offA, g.R, g.K, sAr, sAm, r0, k0, a_w, tid);
+    __syncthreads();  // (the fragments of the slice before have been read)
+    infer_g2_store(As, a, a_k, tid);
+    if (PL) infer_g2_store(As + IG_TM * IG_LD, a2, a_k, tid);
+    infer_g2_store(Bs, bb, b_k, tid);
+    __syncthreads();
+    if (live) {
+#pragma unroll
+      for (int s = 0; s < IG_TK / 32; s++) {
+        const int at = (wm + (lane & 31)) * IG_LD + s * 32 + (lane >> 5) * 16;
+        const infer_v4i fb = *(const infer_v4i*)&Bs[(wn + (lane & 31)) * IG_LD + s * 32 + (lane >> 5) * 16];
+        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(*(const infer_v4i*)&As[at], fb, acc, 0, 0, 0);
+        if (PL) acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(*(const infer_v4i*)&As[IG_TM * IG_LD + at], fb, acc2, 0, 0, 0);
+      }
+    }
+  }
+  const size_t col = n0 + wn + (lane & 31);
+  if (!live || col >= g.N) return;
+  int64_t* op = O + b * lenO + c * g.sOc + col * g.sOn;
+#pragma unroll
+  for (int r = 0; r < 16; r++) {
+    const size_t row = r0 + wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    if (row < g.R) op[row * g.sOr] = PL ? (int64_t)acc2[r] * 128 + acc[r] : (int64_t)acc[r];
+  }
 }
 // Requant::apply: (v * mult + 2^(sh-1)) >> sh clamped to +-127; |v| > 2^bits refuses the sample, as run_model refuses the input (per = words per
 // sample). A refused sample's output is clamped like any other: its int8 copy stays a valid operand of k_infer_gemm_i8
@@ -290,9 +387,9 @@ __global__ __launch_bounds__(256) void k_infer_layernorm(const int64_t* __restri
 // |masked| = low byte | high byte | exponential table index (tv bits) | zero chunks (zc groups of zv bits): table[index], times (chunk == 0) for
 // every group. |x| > 2^24 refuses the sample (per = words per sample; the index is masked: nothing is read outside the table, for any x and any
 // shift): the host's shift step has already refused such a sample, or found it refused and given it zero shifts — the test here then leaves
-// its word as it is
-__global__ __launch_bounds__(256) void k_infer_softmax(const int64_t* __restrict__ x, const int64_t* __restrict__ shift, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n,
-                                                       size_t R, size_t K, int64_t scalar, int64_t neg_inf, unsigned tv, unsigned zc, unsigned zv, unsigned* status, size_t per) {
+// its word as it is. lo, hi: the two planes of a two-plane output (IQ_PLANES; null: none), the left operand of k_infer_gemm2_i8
+__global__ __launch_bounds__(256) void k_infer_softmax(const int64_t* __restrict__ x, const int64_t* __restrict__ shift, const int64_t* __restrict__ table, int64_t* __restrict__ o, int8_t* __restrict__ lo, int8_t* __restrict__ hi,
+                                                       size_t n, size_t R, size_t K, int64_t scalar, int64_t neg_inf, unsigned tv, unsigned zc, unsigned zv, unsigned* status, size_t per) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const size_t row = i / K, j = i % K;
@@ -305,6 +402,7 @@ __global__ __launch_bounds__(256) void k_infer_softmax(const int64_t* __restrict
   r >>= tv;
   for (unsigned z = 0; z < zc; z++) { acc *= (r & ((int64_t(1) << zv) - 1)) == 0 ? 1 : 0; r >>= zv; }
   o[i] = acc;
+  if (lo) { lo[i] = (int8_t)(acc & 127); hi[i] = (int8_t)(acc >> 7); }  // (the planner has seen every table entry within 0..16383)
 }
 // Logits::Argmax (argmax_rows): one wave per row of K words (rows counts samples x rows of a sample); lanes stride over the row and keep (value,
 // index) under "greater, or equal at a smaller index"; the pairs are reduced across the wave by the same rule, so the result is the FIRST maximum
@@ -396,13 +494,14 @@ static const int8_t* infer_const8(const InferProgram& p, InferDeviceState* st, i
 // descriptors][the image of the chunk's trace rows] to the device block and the image's twin, behind the output block, to the pinned one
 struct InferScratch {
   bool in_q = true;     // model inputs within -128..127 (checked on the host, for the whole call): they travel as int8 and count as quantised tensors
-  std::vector<char> q;  // tensor t has an int8 copy
-  std::vector<size_t> off64, off8;
+  std::vector<char> q;  // tensor t in this call: IQ_NO, IQ_YES (an int8 copy) or IQ_PLANES (two planes and NO int8 copy)
+  std::vector<size_t> off64, off8, off8hi;
   size_t chunk = 1, off_in = 0, off_out = 0, off_stat = 0, total = 0, sm_in = 0, sm_stat = 0, pinned_bytes = 0;
   size_t off_taps = 0, off_img = 0, pin_img = 0;  // (tap mode)
   char* dev = nullptr; char* pinned = nullptr;
   int64_t* T64(int t) const { return (int64_t*)(dev + off64[(size_t)t]); }
-  int8_t* T8(int t) const { return q[(size_t)t] ? (int8_t*)(dev + off8[(size_t)t]) : (int8_t*)nullptr; }
+  int8_t* T8(int t) const { return q[(size_t)t] == IQ_YES ? (int8_t*)(dev + off8[(size_t)t]) : (int8_t*)nullptr; }
+  int8_t* TP(int t, int plane) const { return q[(size_t)t] == IQ_PLANES ? (int8_t*)(dev + (plane ? off8hi : off8)[(size_t)t]) : (int8_t*)nullptr; }
   unsigned* status() const { return (unsigned*)(dev + off_stat); }
   uint32_t* sm_status() const { return (uint32_t*)(pinned + sm_in); }
 };
@@ -413,14 +512,14 @@ static InferScratch infer_layout(const InferProgram& p, const int64_t* inputs, s
   InferScratch m;
   if (!inputs) m.in_q = false;
   for (size_t i = 0, n = ninputs * p.input_len; i < n && m.in_q; i++) m.in_q = inputs[i] >= -128 && inputs[i] <= 127;
-  m.q.resize(nt); m.off64.resize(nt); m.off8.resize(nt);
+  m.q.resize(nt); m.off64.resize(nt); m.off8.resize(nt); m.off8hi.resize(nt);
   size_t per_sample = 0;
   auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-  for (size_t t = 0; t < nt; t++) { m.q[t] = p.tensors[t].q == IQ_YES || (p.tensors[t].q == IQ_IF_INPUTS && m.in_q); per_sample += p.tensors[t].len * (m.q[t] ? 9 : 8); }
+  for (size_t t = 0; t < nt; t++) { const int q = p.tensors[t].q; m.q[t] = (char)(q == IQ_IF_INPUTS ? (m.in_q ? IQ_YES : IQ_NO) : q); per_sample += p.tensors[t].len * (m.q[t] == IQ_PLANES ? 10 : m.q[t] ? 9 : 8); }
   per_sample += p.input_len * (m.in_q ? 1 : 8) + p.output_len * 8;
   if (taps) per_sample += p.row_words * 16;  // (the image and its pinned twin)
   const size_t chunk = m.chunk = std::max<size_t>(1, std::min(ninputs, scratch_cap / std::max<size_t>(per_sample, 1)));
-  for (size_t t = 0; t < nt; t++) { m.off64[t] = m.total; m.total += up(chunk * p.tensors[t].len * 8); m.off8[t] = m.total; if (m.q[t]) m.total += up(chunk * p.tensors[t].len); }
+  for (size_t t = 0; t < nt; t++) { m.off64[t] = m.total; m.total += up(chunk * p.tensors[t].len * 8); m.off8[t] = m.total; if (m.q[t]) m.total += up(chunk * p.tensors[t].len); m.off8hi[t] = m.total; if (m.q[t] == IQ_PLANES) m.total += up(chunk * p.tensors[t].len); }
   const size_t in_bytes = chunk * p.input_len * (m.in_q ? 1 : 8), out_bytes = chunk * p.output_len * 8 + chunk * 4;
   m.off_in = m.total; m.total += up(in_bytes);
   m.off_out = m.total; m.off_stat = m.off_out + chunk * p.output_len * 8; m.total += up(out_bytes);
@@ -445,7 +544,7 @@ static uint32_t infer_first_class(const uint32_t* hs, size_t nb) {
 }
 static dim3 infer_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 // one op for the nb samples of the chunk: one launch. launches: by kind, [IO_KINDS + 2]: those of k_infer_gemm_i8, [IO_KINDS + 3]: those of
-// k_infer_conv_i8 (both are counted under their kind as well)
+// k_infer_conv_i8, [IO_KINDS + 4]: those of k_infer_gemm2_i8 (all three are counted under their kind as well)
 static void infer_launch(const InferProgram& p, const InferOp& o, const InferScratch& m, InferDeviceState* st, hipStream_t s, size_t nb, size_t* launches) {
   static const bool no_mfma = getenv("DP_INFER_NO_MFMA") && atoi(getenv("DP_INFER_NO_MFMA"));
   auto c64 = [&](int c) { return infer_const64(p, st, c); };
@@ -453,13 +552,24 @@ static void infer_launch(const InferProgram& p, const InferOp& o, const InferScr
   launches[o.kind]++;
   switch (o.kind) {
     case IO_GEMM:
-      if (!no_mfma && m.q[(size_t)o.in0] && !p.consts[(size_t)o.w].w8.empty()) {
+      if (!no_mfma && m.q[(size_t)o.in0] == IQ_YES && !p.consts[(size_t)o.w].w8.empty()) {
         const size_t M = nb * o.g.R;
         k_infer_gemm_i8<<<dim3((unsigned)((M + IG_TM - 1) / IG_TM), (unsigned)((o.g.N + IG_TN - 1) / IG_TN)), 256, 0, s>>>(m.T8(o.in0), infer_const8(p, st, o.w), c64(o.bias), m.T64(o.out), M, o.g.K, o.g.N);
         launches[IO_KINDS + 2]++;
       } else k_infer_gemm_i64<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), p.tensors[(size_t)o.in0].len, c64(o.w), 0, c64(o.bias), m.T64(o.out), len, nb, o.g);
       break;
-    case IO_GEMM2: k_infer_gemm_i64<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), p.tensors[(size_t)o.in0].len, m.T64(o.in1), p.tensors[(size_t)o.in1].len, nullptr, m.T64(o.out), len, nb, o.g); break;
+    case IO_GEMM2: {
+      const size_t lenA = p.tensors[(size_t)o.in0].len, lenB = p.tensors[(size_t)o.in1].len;
+      const size_t tr = (o.g.R + IG_TM - 1) / IG_TM, tn = (o.g.N + IG_TN - 1) / IG_TN, tiles = nb * o.g.C * tr * tn;
+      const int qa = m.q[(size_t)o.in0];
+      // the planner found a form for both operands (o.d[0]); here: both have their int8 form in this call — only the LEFT one may be two planes
+      if (!no_mfma && (o.d[0] & IG2_OK) && (qa == IQ_YES || qa == IQ_PLANES) && m.q[(size_t)o.in1] == IQ_YES && tiles <= 0x7fffffffu) {
+        if (qa == IQ_PLANES) k_infer_gemm2_i8<true><<<dim3((unsigned)tiles), 256, 0, s>>>(m.TP(o.in0, 0), m.TP(o.in0, 1), lenA, m.T8(o.in1), lenB, m.T64(o.out), len, o.g, (unsigned)tr, (unsigned)tn, (unsigned)o.d[0]);
+        else k_infer_gemm2_i8<false><<<dim3((unsigned)tiles), 256, 0, s>>>(m.T8(o.in0), nullptr, lenA, m.T8(o.in1), lenB, m.T64(o.out), len, o.g, (unsigned)tr, (unsigned)tn, (unsigned)o.d[0]);
+        launches[IO_KINDS + 4]++;
+      } else k_infer_gemm_i64<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), lenA, m.T64(o.in1), lenB, nullptr, m.T64(o.out), len, nb, o.g);
+      break;
+    }
     case IO_REQUANT: k_infer_requant<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.out), m.T8(o.out), n, o.left, o.shift, o.bits, m.status(), len); break;
     case IO_RELU: k_infer_relu<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.out), m.T8(o.out), n); break;
     case IO_ADDC: k_infer_addc<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), m.T64(o.out), n, len, o.left, o.right); break;
@@ -467,7 +577,7 @@ static void infer_launch(const InferProgram& p, const InferOp& o, const InferScr
     case IO_EMBED: k_infer_embed<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), m.T64(o.out), n, o.d[0], o.d[1], m.status(), len); break;
     case IO_MAXPOOL: k_infer_maxpool<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.out), m.T8(o.out), n, o.d[1], o.d[2]); break;
     case IO_CONV:
-      if (!no_mfma && m.q[(size_t)o.in0] && !p.consts[(size_t)o.w].w8.empty()) {  // (the planner made the image: rn is 4 or 8 and the LDS fits)
+      if (!no_mfma && m.q[(size_t)o.in0] == IQ_YES && !p.consts[(size_t)o.w].w8.empty()) {  // (the planner made the image: rn is 4 or 8 and the LDS fits)
         const unsigned kw = (unsigned)o.d[0], kx = (unsigned)o.d[1], rn = (unsigned)o.d[2], nw = (unsigned)o.d[3], ra = (unsigned)o.d[7], K = (unsigned)o.g.K;
         const unsigned strips = (nw * nw + IC_TP - 1) / IC_TP;
         const dim3 grid((unsigned)(nb * strips), (kw + IC_TC - 1) / IC_TC);
@@ -486,7 +596,7 @@ static void infer_launch(const InferProgram& p, const InferOp& o, const InferScr
       k_infer_layernorm<<<infer_grid(rows * 64), 256, 0, s>>>(m.T64(o.in0), c64(o.w), c64(o.bias), c64(o.table), m.T64(o.out), rows, o.d[0], (int64_t)o.d[1], o.left, o.shift, m.status(), len / o.d[0]);
       break;
     }
-    case IO_SOFTMAX: k_infer_softmax<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.in1), c64(o.table), m.T64(o.out), n, o.d[1], o.d[2], o.left, -(((o.right >> 16) + 1) << 16), o.bits, (unsigned)o.d[3], (unsigned)o.d[4], m.status(), len); break;  // (after infer_shift_trip)
+    case IO_SOFTMAX: k_infer_softmax<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.in1), c64(o.table), m.T64(o.out), m.TP(o.out, 0), m.TP(o.out, 1), n, o.d[1], o.d[2], o.left, -(((o.right >> 16) + 1) << 16), o.bits, (unsigned)o.d[3], (unsigned)o.d[4], m.status(), len); break;  // (after infer_shift_trip)
     case IO_ARGMAX: { const size_t rows = nb * o.d[0]; k_infer_argmax<<<infer_grid(rows * 64), 256, 0, s>>>(m.T64(o.in0), m.T8(o.in0), m.T64(o.out), rows, o.d[1]); break; }
     default: throw DpError(DP_ERR_ARG, "dp_model_infer: unknown op");
   }
@@ -542,7 +652,7 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
   double tap_ms = 0;
   const size_t chunk = m.chunk, in_w = m.in_q ? 1 : 8;
   st->c64.resize(p.consts.size(), nullptr); st->c8.resize(p.consts.size(), nullptr);
-  size_t launches[IO_KINDS + 4] = {0}, nchunks = 0, trips = 0, nrefused = 0;
+  size_t launches[IO_KINDS + 5] = {0}, nchunks = 0, trips = 0, nrefused = 0;
   double trip_ms = 0;
   uint32_t stop = INFER_OK;  // plain mode (no `reasons`): the class of the refused sample that ends the call
   auto cleanup = [&] {
@@ -604,9 +714,9 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
   cleanup();
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (wall_ms) *wall_ms = ms;
-  const size_t n_i8 = launches[IO_KINDS + 2], n_i64 = launches[IO_GEMM] + launches[IO_GEMM2] - n_i8;
-  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu conv %zu conv_i8 %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu argmax %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s%s\n",
-                   n_i8, n_i64, launches[IO_CONV], launches[IO_KINDS + 3], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], launches[IO_ARGMAX], trips, trip_ms,
+  const size_t n_i8 = launches[IO_KINDS + 2] + launches[IO_KINDS + 4], n_i64 = launches[IO_GEMM] + launches[IO_GEMM2] - n_i8;
+  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu gemm2_i8 %zu conv %zu conv_i8 %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu argmax %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s%s\n",
+                   n_i8, n_i64, launches[IO_KINDS + 4], launches[IO_CONV], launches[IO_KINDS + 3], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], launches[IO_ARGMAX], trips, trip_ms,
                    ninputs, nchunks, chunk, (double)m.total / 1048576.0, m.in_q ? "int8" : "int64", ms,
                    taps ? ("; taps " + std::to_string(p.taps.size()) + " entries, " + std::to_string(p.row_words) + " words, pack_launches " + std::to_string(tap_launches) + " pack_ms " + std::to_string(tap_ms)).c_str() : "",
                    reasons ? ("; checked, refused " + std::to_string(nrefused)).c_str() : "");
@@ -640,7 +750,7 @@ void hip_infer_decode(Dev* d, const InferProgram& p, InferDeviceState* st, const
   const size_t tok_bytes = up(chunk * seq * 8), word_bytes = up(chunk * 4);
   char* dstate = nullptr; char* pin = nullptr;
   st->c64.resize(p.consts.size(), nullptr); st->c8.resize(p.consts.size(), nullptr);
-  size_t launches[IO_KINDS + 4] = {0}, nchunks = 0, nsteps = 0, nlaunch = 0, npolls = 0, trips = 0;
+  size_t launches[IO_KINDS + 5] = {0}, nchunks = 0, nsteps = 0, nlaunch = 0, npolls = 0, trips = 0;
   double trip_ms = 0, final_ms = 0;
   auto cleanup = [&] {
     (void)hipStreamSynchronize(s);
@@ -707,6 +817,6 @@ void hip_infer_decode(Dev* d, const InferProgram& p, InferDeviceState* st, const
   cleanup();
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (wall_ms) *wall_ms = ms;
-  for (size_t k = 0; k < IO_KINDS + 2; k++) nlaunch += launches[k];  // (launches[IO_KINDS + 2] and [IO_KINDS + 3] count the i8 forms of launches counted under IO_GEMM and IO_CONV)
+  for (size_t k = 0; k < IO_KINDS + 2; k++) nlaunch += launches[k];  // (launches[IO_KINDS + 2], [+ 3] and [+ 4] count the i8 forms of launches counted under IO_GEMM, IO_CONV and IO_GEMM2)
   if (timing) fprintf(stderr, "[dp decode] prompts %zu chunks %zu steps %zu launches %zu polls %zu final_ms %.3f\n", nprompts, nchunks, nsteps, nlaunch, npolls, final_ms);
 }

@@ -35,7 +35,11 @@
  * Prover.prove_batch_screened): dp_model_prove_batch discards every proof of a batch in which the host inference of one input throws.
  *
  * Knobs (environment): DP_INFER_SCRATCH_MB (activation scratch of one chunk of the batch, default 1024), DP_INFER_NO_MFMA=1 (64-bit
- * products and convolutions everywhere), DP_INFER_LOG=1 (one `[dp infer]` line per call on stderr: launches per kernel, chunks, wall time; `conv N` counts
+ * products and convolutions everywhere), DP_INFER_LOG=1 (one `[dp infer]` line per call on stderr: launches per kernel, chunks, wall time; `gemm_i8 N`
+ * counts every product that ran on the i8 MFMA, `gemm_i64 N` the others, and `gemm2_i8 N`, directly after it, those of the first that were
+ * products of two tensors of the batch: a MatMul of two inputs, a ConcatMatMul and the two products of an Mha node take the matrix units when each
+ * operand is contiguous along the summed axis or along its other matrix axis, K * 128 * 128 < 2^31, the right operand is within -128..127 (a
+ * Requant's output, or a model input of a call whose inputs all are) and the left one is too or is a Softmax's output; `conv N` counts
  * every convolution launch and `conv_i8 N`, directly after it, those of them that ran on the i8 MFMA; gelu / layernorm / softmax launches,
  * shift_trips = round trips of the Softmax shift step and shift_ms = the milliseconds spent in them; a checked call appends
  * `; checked, refused N`), DP_PROVE_TRACE_MB (host memory for the trace rows of one segment of dp_model_prove_batch_ex, default 4096).
