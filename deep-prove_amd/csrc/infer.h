@@ -66,7 +66,8 @@ struct InferOp {
   unsigned shift = 0, bits = 0;      // IO_REQUANT; IO_LAYERNORM: shift = range_check_bits; IO_SOFTMAX: bits = table bits
   // IO_EMBED: vocabulary, embedding size; IO_MAXPOOL: c, h, w; IO_CONV: kw, kx, real_nw, nw, unp_out[3], ra (the filter rows of the int8 image; 0: none, the op stays on k_infer_conv); IO_GELU: max; IO_LAYERNORM: row length, N;
   // IO_SOFTMAX: C, R, K, zero chunks, zero vars (in1 = the shift buffer of the chunk, a tensor of C * R words per sample); IO_ARGMAX: rows, K;
-  // IO_GEMM2: d[0] = infer_gemm2_plan (IG2_*; 0: the op stays on k_infer_gemm_i64)
+  // IO_GEMM2: d[0] = infer_gemm2_plan (IG2_*; 0: the op stays on k_infer_gemm_i64); IO_GEMM: d[0] = the ops behind it that k_infer_gemm_i8_rq
+  // absorbs (infer_fuse_plan: 0 none, 1 its Requant, 2 the Requant and a ReLU), d[1], d[2] = their indices in InferProgram::ops
   size_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 // k_infer_conv_i8 (infer_kernels.inc): a workgroup computes IC_TC output channels of a strip of IC_TP consecutive pixels of one sample's plane; the
@@ -107,6 +108,55 @@ struct InferProgram {
   // read and gets zero shifts, a sample with an input beyond 2^24 gets INFER_BAD_SOFTMAX and zero shifts
   std::function<void(const InferOp& o, const int64_t* x, size_t nb, int64_t* shifts, uint32_t* status)> shifts;
 };
+// The tiles of k_infer_gemm2_i8 (64 x 64 per workgroup, one (sample, concat index) each) for nb samples: its grid, which must fit 31 bits
+inline size_t infer_gemm2_tiles(const InferGemmShape& g, size_t nb) { return nb * g.C * ((g.R + 63) / 64) * ((g.N + 63) / 64); }
+// THE predicate "op o reads only the int8 form of tensor t in this call": o is a product that takes an MFMA kernel (k_infer_gemm_i8 /
+// k_infer_gemm_i8_rq, k_infer_conv_i8, k_infer_gemm2_i8 — whose left operand may be two planes instead) or an Argmax that reads the int8 copy.
+// q: the form of every tensor in this call (InferScratch::q), nb: the samples of the chunk, no_mfma: DP_INFER_NO_MFMA. infer_launch dispatches
+// on it and infer_needs_int64 elides by it: what is launched and what is left unwritten cannot drift apart. Every other reader (Add2, LayerNorm,
+// GELU, Softmax, Requant, ReLU, MaxPool, Embeddings, a 64-bit product) reads the int64 form: false.
+inline bool infer_reads_int8_only(const InferProgram& p, const InferOp& o, int t, const std::vector<char>& q, size_t nb, bool no_mfma) {
+  if (t < 0 || (t != o.in0 && t != o.in1)) return false;
+  switch (o.kind) {
+    case IO_GEMM: case IO_CONV: return !no_mfma && t == o.in0 && q[(size_t)o.in0] == IQ_YES && !p.consts[(size_t)o.w].w8.empty();
+    case IO_GEMM2: return !no_mfma && (o.d[0] & IG2_OK) && (q[(size_t)o.in0] == IQ_YES || q[(size_t)o.in0] == IQ_PLANES) && q[(size_t)o.in1] == IQ_YES && infer_gemm2_tiles(o.g, nb) <= 0x7fffffffu;
+    case IO_ARGMAX: return t == o.in0 && q[(size_t)o.in0] == IQ_YES;
+    default: return false;
+  }
+}
+// whether tensor t must exist as int64 in this call: it is a model output, or some op reads more than its int8 form (when in doubt: yes)
+inline bool infer_needs_int64(const InferProgram& p, int t, const std::vector<char>& q, size_t nb, bool no_mfma) {
+  if (std::find(p.outputs.begin(), p.outputs.end(), t) != p.outputs.end()) return true;
+  for (const InferOp& o : p.ops) if ((o.in0 == t || o.in1 == t) && !infer_reads_int8_only(p, o, t, q, nb, no_mfma)) return true;
+  return false;
+}
+// The chains k_infer_gemm_i8_rq serves in one launch, marked on the finished program (the last step of infer_plan): an IO_GEMM whose constant has
+// an int8 copy and whose output has exactly one reader, an IO_REQUANT with shift >= 1, and is no model output; and behind that, where the
+// Requant's output likewise has exactly one reader, an IO_RELU, and is no model output, the ReLU too. The absorbed ops run at the head's place
+// in the order of the ops, so no op in between may be one that refuses data under another class (Embeddings, GELU, LayerNorm, Softmax): the
+// status word holds the class of the FIRST op that refused a sample. Whether the head's input has its int8 form, and whether the chain's last
+// tensor still needs its int64 form, is known per call only (infer_launch).
+inline void infer_fuse_plan(InferProgram& p) {
+  const size_t nt = p.tensors.size(), no = p.ops.size();
+  std::vector<int> readers(nt, 0), reader(nt, -1);
+  for (size_t i = 0; i < no; i++) for (int t : {p.ops[i].in0, p.ops[i].in1}) if (t >= 0) { readers[(size_t)t]++; reader[(size_t)t] = (int)i; }
+  for (int t : p.outputs) readers[(size_t)t] += 2;  // (a model output is never a tensor with ONE reader)
+  // the only reader of tensor t, when it is an op of `kind` behind op `from` with no refusing op of another class between the two; else -1
+  auto sole = [&](int t, int kind, size_t from) {
+    const int j = readers[(size_t)t] == 1 ? reader[(size_t)t] : -1;
+    if (j < 0 || (size_t)j <= from || p.ops[(size_t)j].kind != kind || p.ops[(size_t)j].in0 != t) return -1;
+    for (size_t k = from + 1; k < (size_t)j; k++) { const int kk = p.ops[k].kind; if (kk == IO_EMBED || kk == IO_GELU || kk == IO_LAYERNORM || kk == IO_SOFTMAX) return -1; }
+    return j;
+  };
+  for (size_t i = 0; i < no; i++) {
+    InferOp& o = p.ops[i];
+    if (o.kind != IO_GEMM || p.consts[(size_t)o.w].w8.empty()) continue;
+    const int rq = sole(o.out, IO_REQUANT, i);
+    if (rq < 0 || p.ops[(size_t)rq].shift < 1) continue;
+    const int rl = sole(p.ops[(size_t)rq].out, IO_RELU, i);
+    o.d[0] = rl < 0 ? 1 : 2; o.d[1] = (size_t)rq; o.d[2] = rl < 0 ? 0 : (size_t)rl;
+  }
+}
 struct InferDeviceState;  // the constants on the device (made at the first call, freed with the model)
 InferDeviceState* hip_infer_state_new(int device);
 void hip_infer_state_free(InferDeviceState* s);
@@ -396,6 +446,7 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
     const LayerSpec& l = m.layers[(size_t)o.node];
     infer_softmax_shifts(l.kind == L_MHA ? mha_softmax_spec(l) : l, x, nb, shifts, status);
   };
+  infer_fuse_plan(p);
   return p;
 }
 #endif

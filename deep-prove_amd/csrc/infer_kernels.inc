@@ -210,6 +210,106 @@ __global__ __launch_bounds__(256) void k_infer_relu(const int64_t* __restrict__ 
   o[i] = v;
   if (o8) o8[i] = (int8_t)v;
 }
+// A Dense / MatMul / QKV product with the Requant behind it (and the ReLU behind that: RELU) in ONE launch: C = A[M][K] (int8) * Bt[N][K]^T (int8)
+// + bias[N] on v_mfma_i32_32x32x32_i8, exact under the rule of weight_const (K * 128 * 128 < 2^31), then in registers what k_infer_requant does,
+// letter for letter: |v| > 2^bits refuses the sample, (v * mult + 2^(sh-1)) >> sh with the multiply and add in unsigned 64-bit arithmetic and an
+// arithmetic shift, clamp to +-127; then max(., 0). O8 — the int8 copy of the chain's LAST tensor — is always written, its int64 form O64 only
+// under W64 (infer_needs_int64); the int64 product and the Requant's tensor under a ReLU are never written. 1 byte per element instead of 42.
+// Staging: the operands go through LDS in K slices of RQ_TK = 128 (four MFMA per wave between two barriers; k_infer_gemm_i8: two). A thread
+//   stages 2 x 16 bytes of each operand and holds the NEXT slice's 64 bytes in registers: their global loads are issued right behind the
+//   barrier that publishes the current slice and are in flight while it is multiplied. One LDS buffer, not two: the second costs as much LDS
+//   as the registers cost nothing (below), and the store of a prefetched slice is 4 ds_write_b128 per thread. MFMA steps beyond K are skipped.
+// Tile: 64 x 64 per workgroup of 4 waves (32 x 32 each), as k_infer_gemm_i8. The shapes that matter are M = batch x rows in the thousands with
+//   N = 256 .. 1024 (the transformer layer at 320 inputs: M * N / 4096 = a few hundred tiles for 256 CUs) and N = 3 .. 10 (the last Dense of
+//   Dense-4M and CNN-264k: one column tile). A 128-row tile would halve the traffic of Bt but leave half the CUs without a workgroup on the
+//   former and change nothing on the latter; 64 x 64 keeps 16 accumulator registers and 18 KB of LDS, so several workgroups share a CU and one's
+//   epilogue and prefetch latency hide under another's MFMA.
+// Epilogue: lane l holds one column and 16 rows of D (column = l & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (l >> 5)). The requantised tile goes
+//   through LDS as [64][RQ_LDC] bytes — the operand buffers are free behind a barrier after the last slice — and leaves row-contiguous: O8 in
+//   16-byte vectors where N % 16 == 0 (the int8 copy of a tensor starts 256-aligned, its row pitch is N, a column tile starts at a multiple of
+//   64), bytes otherwise; O64 in 16-byte pairs where N is even, words otherwise, consecutive lanes at consecutive addresses.
+// Refusal: row `row` belongs to sample row / R (R = o.g.R; M = samples x R). A lane ORs its 16 tests into a mask; ONE ballot per wave decides,
+//   and only a wave with a bad element walks its masks to infer_refuse (INFER_BAD_REQUANT). Rows >= M, columns >= N and k >= K are zero-filled
+//   in registers before they reach LDS (infer_ld16; nothing is read past a matrix) and are never tested, stored or flagged. A refused sample's
+//   output is clamped like any other: its int8 copy stays a valid operand (the invariant of k_infer_requant).
+// Fragments: as k_infer_gemm_i8 — lane l holds 16 consecutive k (16 * (l >> 5) ...) of row l & 31 of A and of column l & 31 of B, the SAME rule.
+constexpr int RQ_TK = 128, RQ_LD = RQ_TK + 16, RQ_LDC = IG_TN + 16;  // K slice, LDS row pitch of the operands and of the result tile, in bytes
+typedef long long infer_v2l __attribute__((ext_vector_type(2)));
+template <bool RELU, bool W64> __global__ __launch_bounds__(256) void k_infer_gemm_i8_rq(const int8_t* __restrict__ A, const int8_t* __restrict__ Bt, const int64_t* __restrict__ bias, int8_t* __restrict__ O8,
+                                                                                      int64_t* __restrict__ O64, size_t M, size_t K, size_t N, int64_t mult, unsigned sh, unsigned bits, unsigned* status, size_t R) {
+  __shared__ __attribute__((aligned(16))) int8_t lds[(IG_TM + IG_TN) * RQ_LD];
+  int8_t* As = lds; int8_t* Bs = lds + IG_TM * RQ_LD; int8_t* Cs = lds;  // (Cs: [IG_TM][RQ_LDC], after the last slice)
+  static_assert(IG_TM * RQ_LDC <= (IG_TM + IG_TN) * RQ_LD && IG_TM == 64 && IG_TN == 64, "the result tile lies in the operand buffers");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t m0 = (size_t)blockIdx.x * IG_TM, n0 = (size_t)blockIdx.y * IG_TN;
+  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
+  const int lr = tid >> 3, lc = (tid & 7) * 16;  // the bytes of a slice this thread stages: tile rows lr and lr + 32, byte column lc
+  const bool k16 = (K & 15) == 0;
+  infer_v16i acc;
+#pragma unroll
+  for (int r = 0; r < 16; r++) acc[r] = 0;
+  infer_v4i a0 = infer_ld16(A, M, K, m0 + lr, lc, k16), a1 = infer_ld16(A, M, K, m0 + lr + 32, lc, k16);
+  infer_v4i b0 = infer_ld16(Bt, N, K, n0 + lr, lc, k16), b1 = infer_ld16(Bt, N, K, n0 + lr + 32, lc, k16);
+  for (size_t k0 = 0; k0 < K; k0 += RQ_TK) {
+    __syncthreads();  // (the fragments of the slice before have been read)
+    *(infer_v4i*)&As[lr * RQ_LD + lc] = a0; *(infer_v4i*)&As[(lr + 32) * RQ_LD + lc] = a1;
+    *(infer_v4i*)&Bs[lr * RQ_LD + lc] = b0; *(infer_v4i*)&Bs[(lr + 32) * RQ_LD + lc] = b1;
+    __syncthreads();
+    const size_t kn = k0 + RQ_TK + lc;  // the next slice: zeros, and no load, at kn >= K
+    a0 = infer_ld16(A, M, K, m0 + lr, kn, k16); a1 = infer_ld16(A, M, K, m0 + lr + 32, kn, k16);
+    b0 = infer_ld16(Bt, N, K, n0 + lr, kn, k16); b1 = infer_ld16(Bt, N, K, n0 + lr + 32, kn, k16);
+#pragma unroll
+    for (int s = 0; s < RQ_TK / 32; s++) {
+      if (k0 + s * 32 < K) {  // (uniform)
+        const infer_v4i fa = *(const infer_v4i*)&As[(wm + (lane & 31)) * RQ_LD + s * 32 + (lane >> 5) * 16];
+        const infer_v4i fb = *(const infer_v4i*)&Bs[(wn + (lane & 31)) * RQ_LD + s * 32 + (lane >> 5) * 16];
+        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa, fb, acc, 0, 0, 0);
+      }
+    }
+  }
+  __syncthreads();  // (every wave has read its last fragments: the operand buffers become the result tile)
+  const size_t col = n0 + wn + (lane & 31);
+  const uint64_t bv = bias && col < N ? (uint64_t)bias[col] : 0, lim = uint64_t(1) << bits;
+  unsigned bad = 0;
+#pragma unroll
+  for (int r = 0; r < 16; r++) {
+    const int tr = wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    const int64_t v = (int64_t)((uint64_t)(int64_t)acc[r] + bv);
+    const uint64_t mag = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
+    if (mag > lim && m0 + tr < M && col < N) bad |= 1u << r;
+    int64_t y = (int64_t)((uint64_t)v * (uint64_t)mult + (uint64_t(1) << (sh - 1))) >> sh;
+    y = y < -127 ? -127 : y > 127 ? 127 : y;
+    if (RELU) y = y < 0 ? 0 : y;
+    Cs[tr * RQ_LDC + wn + (lane & 31)] = (int8_t)y;
+  }
+  if (__ballot(bad != 0)) {
+#pragma unroll
+    for (int r = 0; r < 16; r++) if ((bad >> r) & 1) infer_refuse(status, (m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) / R, INFER_BAD_REQUANT);
+  }
+  __syncthreads();
+  if ((N & 15) == 0) {  // one 16-byte vector of a row per thread
+    const size_t row = m0 + (tid >> 2), c = n0 + (tid & 3) * 16;
+    if (row < M && c < N) *(infer_v4i*)(O8 + row * N + c) = *(const infer_v4i*)&Cs[(tid >> 2) * RQ_LDC + (tid & 3) * 16];
+  } else {
+    for (int i = tid; i < IG_TM * IG_TN; i += 256) {
+      const size_t row = m0 + (i >> 6), c = n0 + (i & 63);
+      if (row < M && c < N) O8[row * N + c] = Cs[(i >> 6) * RQ_LDC + (i & 63)];
+    }
+  }
+  if (!W64) return;
+  if ((N & 1) == 0) {  // (the int64 form of a tensor starts 256-aligned: an even column of any row is 16-aligned)
+    for (int i = tid; i < IG_TM * IG_TN / 2; i += 256) {
+      const size_t row = m0 + (i >> 5), c = n0 + (i & 31) * 2;
+      const int8_t* y = &Cs[(i >> 5) * RQ_LDC + (i & 31) * 2];
+      if (row < M && c < N) { infer_v2l v; v[0] = y[0]; v[1] = y[1]; *(infer_v2l*)(O64 + row * N + c) = v; }
+    }
+  } else {
+    for (int i = tid; i < IG_TM * IG_TN; i += 256) {
+      const size_t row = m0 + (i >> 6), c = n0 + (i & 63);
+      if (row < M && c < N) O64[row * N + c] = Cs[(i >> 6) * RQ_LDC + (i & 63)];
+    }
+  }
+}
 // Add with a static operand / Positional::Learned: left * x + right * w[i mod len] (w: the operand, or the first rows of the table)
 __global__ __launch_bounds__(256) void k_infer_addc(const int64_t* __restrict__ x, const int64_t* __restrict__ w, int64_t* __restrict__ o, size_t n, size_t len, int64_t left, int64_t right) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -543,28 +643,45 @@ static uint32_t infer_first_class(const uint32_t* hs, size_t nb) {
   return INFER_OK;
 }
 static dim3 infer_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
-// one op for the nb samples of the chunk: one launch. launches: by kind, [IO_KINDS + 2]: those of k_infer_gemm_i8, [IO_KINDS + 3]: those of
-// k_infer_conv_i8, [IO_KINDS + 4]: those of k_infer_gemm2_i8 (all three are counted under their kind as well)
-static void infer_launch(const InferProgram& p, const InferOp& o, const InferScratch& m, InferDeviceState* st, hipStream_t s, size_t nb, size_t* launches) {
+// one op for the nb samples of the chunk: one launch. launches (INFER_COUNTS words): by kind the ops served, [IO_KINDS + 2]: the launches of
+// k_infer_gemm_i8 and k_infer_gemm_i8_rq, [IO_KINDS + 3]: those of k_infer_conv_i8, [IO_KINDS + 4]: those of k_infer_gemm2_i8 (all counted
+// under their kind as well), [IO_KINDS + 5]: those of k_infer_gemm_i8_rq, [IO_KINDS + 6]: the ops it absorbed — served, and counted under
+// their kinds, without a launch of their own. fuse: the head of a chain (infer_fuse_plan) whose input has its int8 form in this call takes
+// k_infer_gemm_i8_rq; the result is the number of ops absorbed (o.d[1], o.d[2]: the caller skips them), 0 for every other launch.
+constexpr size_t INFER_COUNTS = IO_KINDS + 7;
+static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferScratch& m, InferDeviceState* st, hipStream_t s, size_t nb, size_t* launches, bool fuse) {
   static const bool no_mfma = getenv("DP_INFER_NO_MFMA") && atoi(getenv("DP_INFER_NO_MFMA"));
+  const bool i8 = infer_reads_int8_only(p, o, o.in0, m.q, nb, no_mfma);  // (the one predicate: also what infer_needs_int64 elides by)
   auto c64 = [&](int c) { return infer_const64(p, st, c); };
   const size_t len = p.tensors[(size_t)o.out].len, n = nb * len;
   launches[o.kind]++;
   switch (o.kind) {
     case IO_GEMM:
-      if (!no_mfma && m.q[(size_t)o.in0] == IQ_YES && !p.consts[(size_t)o.w].w8.empty()) {
+      if (i8) {
         const size_t M = nb * o.g.R;
-        k_infer_gemm_i8<<<dim3((unsigned)((M + IG_TM - 1) / IG_TM), (unsigned)((o.g.N + IG_TN - 1) / IG_TN)), 256, 0, s>>>(m.T8(o.in0), infer_const8(p, st, o.w), c64(o.bias), m.T64(o.out), M, o.g.K, o.g.N);
+        const dim3 grid((unsigned)((M + IG_TM - 1) / IG_TM), (unsigned)((o.g.N + IG_TN - 1) / IG_TN));
         launches[IO_KINDS + 2]++;
+        if (fuse && o.d[0]) {
+          const InferOp& rq = p.ops[o.d[1]];
+          const bool relu = o.d[0] == 2;
+          const int last = relu ? p.ops[o.d[2]].out : rq.out;
+          int64_t* o64 = infer_needs_int64(p, last, m.q, nb, no_mfma) ? m.T64(last) : nullptr;
+          auto go = [&](auto kern) { kern<<<grid, 256, 0, s>>>(m.T8(o.in0), infer_const8(p, st, o.w), c64(o.bias), m.T8(last), o64, M, o.g.K, o.g.N, rq.left, rq.shift, rq.bits, m.status(), o.g.R); };
+          if (relu) { if (o64) go(k_infer_gemm_i8_rq<true, true>); else go(k_infer_gemm_i8_rq<true, false>); }
+          else { if (o64) go(k_infer_gemm_i8_rq<false, true>); else go(k_infer_gemm_i8_rq<false, false>); }
+          launches[IO_REQUANT]++; launches[IO_RELU] += relu; launches[IO_KINDS + 5]++; launches[IO_KINDS + 6] += o.d[0];
+          return o.d[0];
+        }
+        k_infer_gemm_i8<<<grid, 256, 0, s>>>(m.T8(o.in0), infer_const8(p, st, o.w), c64(o.bias), m.T64(o.out), M, o.g.K, o.g.N);
       } else k_infer_gemm_i64<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), p.tensors[(size_t)o.in0].len, c64(o.w), 0, c64(o.bias), m.T64(o.out), len, nb, o.g);
       break;
     case IO_GEMM2: {
       const size_t lenA = p.tensors[(size_t)o.in0].len, lenB = p.tensors[(size_t)o.in1].len;
-      const size_t tr = (o.g.R + IG_TM - 1) / IG_TM, tn = (o.g.N + IG_TN - 1) / IG_TN, tiles = nb * o.g.C * tr * tn;
-      const int qa = m.q[(size_t)o.in0];
-      // the planner found a form for both operands (o.d[0]); here: both have their int8 form in this call — only the LEFT one may be two planes
-      if (!no_mfma && (o.d[0] & IG2_OK) && (qa == IQ_YES || qa == IQ_PLANES) && m.q[(size_t)o.in1] == IQ_YES && tiles <= 0x7fffffffu) {
-        if (qa == IQ_PLANES) k_infer_gemm2_i8<true><<<dim3((unsigned)tiles), 256, 0, s>>>(m.TP(o.in0, 0), m.TP(o.in0, 1), lenA, m.T8(o.in1), lenB, m.T64(o.out), len, o.g, (unsigned)tr, (unsigned)tn, (unsigned)o.d[0]);
+      const size_t tr = (o.g.R + IG_TM - 1) / IG_TM, tn = (o.g.N + IG_TN - 1) / IG_TN, tiles = infer_gemm2_tiles(o.g, nb);
+      static_assert(IG_TM == 64 && IG_TN == 64, "infer_gemm2_tiles counts 64 x 64 tiles");
+      // the planner found a form for both operands (o.d[0]); i8: both have their int8 form in this call — only the LEFT one may be two planes
+      if (i8) {
+        if (m.q[(size_t)o.in0] == IQ_PLANES) k_infer_gemm2_i8<true><<<dim3((unsigned)tiles), 256, 0, s>>>(m.TP(o.in0, 0), m.TP(o.in0, 1), lenA, m.T8(o.in1), lenB, m.T64(o.out), len, o.g, (unsigned)tr, (unsigned)tn, (unsigned)o.d[0]);
         else k_infer_gemm2_i8<false><<<dim3((unsigned)tiles), 256, 0, s>>>(m.T8(o.in0), nullptr, lenA, m.T8(o.in1), lenB, m.T64(o.out), len, o.g, (unsigned)tr, (unsigned)tn, (unsigned)o.d[0]);
         launches[IO_KINDS + 4]++;
       } else k_infer_gemm_i64<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), lenA, m.T64(o.in1), lenB, nullptr, m.T64(o.out), len, nb, o.g);
@@ -577,7 +694,7 @@ static void infer_launch(const InferProgram& p, const InferOp& o, const InferScr
     case IO_EMBED: k_infer_embed<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), m.T64(o.out), n, o.d[0], o.d[1], m.status(), len); break;
     case IO_MAXPOOL: k_infer_maxpool<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.out), m.T8(o.out), n, o.d[1], o.d[2]); break;
     case IO_CONV:
-      if (!no_mfma && m.q[(size_t)o.in0] == IQ_YES && !p.consts[(size_t)o.w].w8.empty()) {  // (the planner made the image: rn is 4 or 8 and the LDS fits)
+      if (i8) {  // (the planner made the image: rn is 4 or 8 and the LDS fits)
         const unsigned kw = (unsigned)o.d[0], kx = (unsigned)o.d[1], rn = (unsigned)o.d[2], nw = (unsigned)o.d[3], ra = (unsigned)o.d[7], K = (unsigned)o.g.K;
         const unsigned strips = (nw * nw + IC_TP - 1) / IC_TP;
         const dim3 grid((unsigned)(nb * strips), (kw + IC_TC - 1) / IC_TC);
@@ -597,9 +714,10 @@ static void infer_launch(const InferProgram& p, const InferOp& o, const InferScr
       break;
     }
     case IO_SOFTMAX: k_infer_softmax<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.in1), c64(o.table), m.T64(o.out), m.TP(o.out, 0), m.TP(o.out, 1), n, o.d[1], o.d[2], o.left, -(((o.right >> 16) + 1) << 16), o.bits, (unsigned)o.d[3], (unsigned)o.d[4], m.status(), len); break;  // (after infer_shift_trip)
-    case IO_ARGMAX: { const size_t rows = nb * o.d[0]; k_infer_argmax<<<infer_grid(rows * 64), 256, 0, s>>>(m.T64(o.in0), m.T8(o.in0), m.T64(o.out), rows, o.d[1]); break; }
+    case IO_ARGMAX: { const size_t rows = nb * o.d[0]; k_infer_argmax<<<infer_grid(rows * 64), 256, 0, s>>>(m.T64(o.in0), i8 ? m.T8(o.in0) : nullptr, m.T64(o.out), rows, o.d[1]); break; }
     default: throw DpError(DP_ERR_ARG, "dp_model_infer: unknown op");
   }
+  return 0;
 }
 // The round trip in front of an IO_SOFTMAX: the shift of every row is made on the host, by the function the host inference calls. The status
 // words come down with the Softmax input: the samples refused so far are skipped (their rows are not read), those the range check refuses here
@@ -618,21 +736,26 @@ static void infer_shift_trip(const InferProgram& p, const InferOp& o, const Infe
 // The program for the nb samples of the chunk whose input block is on the device: the loads of the model inputs, then every op in order, with
 // the round trip in front of each IO_SOFTMAX (the only host synchronisation here: a program without one is enqueued and nothing waits).
 // Plain mode (not checked): the class of the refused sample a shift step found, which ends the call; the later ops are not enqueued then
-static uint32_t infer_enqueue(const InferProgram& p, const InferScratch& m, InferDeviceState* st, hipStream_t s, size_t nb, bool checked, size_t* launches, size_t& trips, double& trip_ms) {
+static uint32_t infer_enqueue(const InferProgram& p, const InferScratch& m, InferDeviceState* st, hipStream_t s, size_t nb, bool checked, size_t* launches, size_t& trips, double& trip_ms, bool taps = false) {
+  static const bool no_fuse = getenv("DP_INFER_NO_FUSE") && atoi(getenv("DP_INFER_NO_FUSE"));
+  const bool fuse = !no_fuse && !taps;  // (tap mode: every tensor is an entry of the trace row, nothing is elided)
+  std::vector<char> absorbed(p.ops.size(), 0);
   size_t ioff = 0;
   for (int t : p.inputs) {
     const size_t len = p.tensors[(size_t)t].len, n = nb * len;
     k_infer_load<<<infer_grid(n), 256, 0, s>>>(m.in_q ? nullptr : (const int64_t*)(m.dev + m.off_in), m.in_q ? (const int8_t*)(m.dev + m.off_in) : nullptr, p.input_len, ioff, len, m.T64(t), m.T8(t), n);
     ioff += len; launches[IO_KINDS]++;
   }
-  for (const InferOp& o : p.ops) {
+  for (size_t i = 0; i < p.ops.size(); i++) {
+    const InferOp& o = p.ops[i];
+    if (absorbed[i]) continue;  // (a Requant / ReLU the fused launch of its chain's head has served)
     if (o.kind == IO_SOFTMAX) {
       const auto ts = std::chrono::steady_clock::now();
       infer_shift_trip(p, o, m, s, nb);
       trips++; trip_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
       if (!checked) if (const uint32_t cls = infer_first_class(m.sm_status(), nb)) return cls;
     }
-    infer_launch(p, o, m, st, s, nb, launches);
+    for (size_t k = infer_launch(p, o, m, st, s, nb, launches, fuse); k >= 1; k--) absorbed[o.d[k]] = 1;
   }
   return INFER_OK;
 }
@@ -652,7 +775,7 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
   double tap_ms = 0;
   const size_t chunk = m.chunk, in_w = m.in_q ? 1 : 8;
   st->c64.resize(p.consts.size(), nullptr); st->c8.resize(p.consts.size(), nullptr);
-  size_t launches[IO_KINDS + 5] = {0}, nchunks = 0, trips = 0, nrefused = 0;
+  size_t launches[INFER_COUNTS] = {0}, nchunks = 0, trips = 0, nrefused = 0;
   double trip_ms = 0;
   uint32_t stop = INFER_OK;  // plain mode (no `reasons`): the class of the refused sample that ends the call
   auto cleanup = [&] {
@@ -678,7 +801,7 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
       else memcpy(m.pinned, inputs + b0 * p.input_len, nin * 8);
       HIP_CHECK(hipMemcpyAsync(m.dev + m.off_in, m.pinned, nin * in_w, hipMemcpyHostToDevice, s));
       HIP_CHECK(hipMemsetAsync(m.status(), 0, nb * 4, s));
-      if ((stop = infer_enqueue(p, m, st, s, nb, reasons != nullptr, launches, trips, trip_ms))) break;
+      if ((stop = infer_enqueue(p, m, st, s, nb, reasons != nullptr, launches, trips, trip_ms, taps))) break;
       size_t ooff = 0;
       for (int t : p.outputs) {
         const size_t len = p.tensors[(size_t)t].len, n = nb * len;
@@ -715,8 +838,8 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (wall_ms) *wall_ms = ms;
   const size_t n_i8 = launches[IO_KINDS + 2] + launches[IO_KINDS + 4], n_i64 = launches[IO_GEMM] + launches[IO_GEMM2] - n_i8;
-  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu gemm2_i8 %zu conv %zu conv_i8 %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu argmax %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s%s\n",
-                   n_i8, n_i64, launches[IO_KINDS + 4], launches[IO_CONV], launches[IO_KINDS + 3], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], launches[IO_ARGMAX], trips, trip_ms,
+  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu gemm2_i8 %zu conv %zu conv_i8 %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu argmax %zu fused %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s%s\n",
+                   n_i8, n_i64, launches[IO_KINDS + 4], launches[IO_CONV], launches[IO_KINDS + 3], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], launches[IO_ARGMAX], launches[IO_KINDS + 5], trips, trip_ms,
                    ninputs, nchunks, chunk, (double)m.total / 1048576.0, m.in_q ? "int8" : "int64", ms,
                    taps ? ("; taps " + std::to_string(p.taps.size()) + " entries, " + std::to_string(p.row_words) + " words, pack_launches " + std::to_string(tap_launches) + " pack_ms " + std::to_string(tap_ms)).c_str() : "",
                    reasons ? ("; checked, refused " + std::to_string(nrefused)).c_str() : "");
@@ -750,7 +873,7 @@ void hip_infer_decode(Dev* d, const InferProgram& p, InferDeviceState* st, const
   const size_t tok_bytes = up(chunk * seq * 8), word_bytes = up(chunk * 4);
   char* dstate = nullptr; char* pin = nullptr;
   st->c64.resize(p.consts.size(), nullptr); st->c8.resize(p.consts.size(), nullptr);
-  size_t launches[IO_KINDS + 5] = {0}, nchunks = 0, nsteps = 0, nlaunch = 0, npolls = 0, trips = 0;
+  size_t launches[INFER_COUNTS] = {0}, nchunks = 0, nsteps = 0, nlaunch = 0, npolls = 0, trips = 0;
   double trip_ms = 0, final_ms = 0;
   auto cleanup = [&] {
     (void)hipStreamSynchronize(s);
@@ -817,6 +940,7 @@ void hip_infer_decode(Dev* d, const InferProgram& p, InferDeviceState* st, const
   cleanup();
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (wall_ms) *wall_ms = ms;
-  for (size_t k = 0; k < IO_KINDS + 2; k++) nlaunch += launches[k];  // (launches[IO_KINDS + 2], [+ 3] and [+ 4] count the i8 forms of launches counted under IO_GEMM, IO_CONV and IO_GEMM2)
+  for (size_t k = 0; k < IO_KINDS + 2; k++) nlaunch += launches[k];  // (launches[IO_KINDS + 2] .. [+ 5] count the i8 forms of launches counted under IO_GEMM, IO_CONV and IO_GEMM2)
+  nlaunch -= launches[IO_KINDS + 6];  // (ops a fused launch absorbed: served without a launch)
   if (timing) fprintf(stderr, "[dp decode] prompts %zu chunks %zu steps %zu launches %zu polls %zu final_ms %.3f\n", nprompts, nchunks, nsteps, nlaunch, npolls, final_ms);
 }
