@@ -2,11 +2,13 @@
 // The host flattens a ModelSpec into an InferProgram (infer_plan below: tensors, constants, one op per launch) once per model; hip_infer_run
 // (infer_kernels.inc, compiled into hip_dev.hip) executes it for a batch: activations are [batch][tensor], one launch serves the whole batch.
 // Which products take the i8 MFMA is decided here, statically: the weights within -128..127, K * 128 * 128 < 2^31 and the input produced by
-// a Requant (through ReLU / MaxPool / Flatten) or a model input the host has range-checked at upload. A convolution is such a product too
+// a Requant (through ReLU / MaxPool / Flatten), a model input the host has range-checked at upload, or a tensor whose values are bounded
+// whatever the data is (infer_range_plan below: the entries of a GELU or Embeddings table and sums of such): within -128..127 it gets an int8
+// copy, within -16384..16383 two int8 planes, the left operand of k_infer_gemm_i8_pl. A convolution is such a product too
 // (k_infer_conv_i8, on the packed filter image of infer_conv_pack) when its padded kernel side is 4 or 8. Everything else is 64-bit
 // multiply-add with the host's wrap-around. The product of two tensors of the batch (IO_GEMM2: MatMul2, ConcatMatMul, the two products of an Mha node)
 // takes k_infer_gemm2_i8 when infer_gemm2_plan below finds a form for both operands and both have int8 copies; the left one may instead be a
-// two-plane tensor (IQ_PLANES: the probabilities a Softmax writes, when every entry of its table lies in 0..16383).
+// two-plane tensor (IQ_PLANES: the probabilities a Softmax writes, when every entry of its table lies in 0..16383, or a tensor of infer_range_plan).
 // INFER_ALL_KINDS (dp_model_infer_ex, DP_INFER_ALL_KINDS) adds LayerNorm, Softmax, Mha and GELU. Their tables are constants of the model, made
 // here by the functions the prover uses (gelu_lut, inv_sqrt_lut, softmax_lut); on the device the three layers are integer work. The one float
 // computation that depends on the data, the shift of a Softmax row, stays on the host: at an IO_SOFTMAX hip_infer_run downloads the input of
@@ -34,8 +36,9 @@
 
 namespace dp {
 
-// every value of the tensor within -128..127: never / always / iff the model inputs of the call are; IQ_PLANES: every value within 0..16383, the
-// tensor has two int8 planes (lo = v & 127, hi = v >> 7) and NO int8 copy — only the left operand of k_infer_gemm2_i8 reads them
+// every value of the tensor within -128..127: never / always / iff the model inputs of the call are; IQ_PLANES: every value within -16384..16383,
+// the tensor has two int8 planes (lo = v & 127 in 0..127, hi = v >> 7 arithmetic in -128..127: v = 128 * hi + lo exactly) and NO int8 copy — only
+// the left operand of k_infer_gemm2_i8 and of k_infer_gemm_i8_pl reads them
 enum InferQ { IQ_NO = 0, IQ_YES = 1, IQ_IF_INPUTS = 2, IQ_PLANES = 3 };
 struct InferTensor { size_t len = 0; int q = IQ_NO; };
 // what ReLU / MaxPool make of their input's form: they keep -128..127 and write the int8 copy themselves; they write no planes
@@ -111,14 +114,16 @@ struct InferProgram {
 // The tiles of k_infer_gemm2_i8 (64 x 64 per workgroup, one (sample, concat index) each) for nb samples: its grid, which must fit 31 bits
 inline size_t infer_gemm2_tiles(const InferGemmShape& g, size_t nb) { return nb * g.C * ((g.R + 63) / 64) * ((g.N + 63) / 64); }
 // THE predicate "op o reads only the int8 form of tensor t in this call": o is a product that takes an MFMA kernel (k_infer_gemm_i8 /
-// k_infer_gemm_i8_rq, k_infer_conv_i8, k_infer_gemm2_i8 — whose left operand may be two planes instead) or an Argmax that reads the int8 copy.
+// k_infer_gemm_i8_rq or, on a two-plane input, k_infer_gemm_i8_pl; k_infer_conv_i8; k_infer_gemm2_i8 — whose left operand may be two planes
+// instead) or an Argmax that reads the int8 copy.
 // q: the form of every tensor in this call (InferScratch::q), nb: the samples of the chunk, no_mfma: DP_INFER_NO_MFMA. infer_launch dispatches
 // on it and infer_needs_int64 elides by it: what is launched and what is left unwritten cannot drift apart. Every other reader (Add2, LayerNorm,
 // GELU, Softmax, Requant, ReLU, MaxPool, Embeddings, a 64-bit product) reads the int64 form: false.
 inline bool infer_reads_int8_only(const InferProgram& p, const InferOp& o, int t, const std::vector<char>& q, size_t nb, bool no_mfma) {
   if (t < 0 || (t != o.in0 && t != o.in1)) return false;
   switch (o.kind) {
-    case IO_GEMM: case IO_CONV: return !no_mfma && t == o.in0 && q[(size_t)o.in0] == IQ_YES && !p.consts[(size_t)o.w].w8.empty();
+    case IO_GEMM: return !no_mfma && t == o.in0 && (q[(size_t)o.in0] == IQ_YES || q[(size_t)o.in0] == IQ_PLANES) && !p.consts[(size_t)o.w].w8.empty();
+    case IO_CONV: return !no_mfma && t == o.in0 && q[(size_t)o.in0] == IQ_YES && !p.consts[(size_t)o.w].w8.empty();
     case IO_GEMM2: return !no_mfma && (o.d[0] & IG2_OK) && (q[(size_t)o.in0] == IQ_YES || q[(size_t)o.in0] == IQ_PLANES) && q[(size_t)o.in1] == IQ_YES && infer_gemm2_tiles(o.g, nb) <= 0x7fffffffu;
     case IO_ARGMAX: return t == o.in0 && q[(size_t)o.in0] == IQ_YES;
     default: return false;
@@ -155,6 +160,67 @@ inline void infer_fuse_plan(InferProgram& p) {
     if (rq < 0 || p.ops[(size_t)rq].shift < 1) continue;
     const int rl = sole(p.ops[(size_t)rq].out, IO_RELU, i);
     o.d[0] = rl < 0 ? 1 : 2; o.d[1] = (size_t)rq; o.d[2] = rl < 0 ? 0 : (size_t)rl;
+  }
+}
+// Static value ranges, on the finished program (in front of infer_fuse_plan): every tensor gets an interval [lo, hi] that holds for ANY input
+// data, refused samples included (what a refusing kernel writes for a refused element is named at each rule), or stays unknown:
+//   Requant: -127..127 (the clamp); ReLU: its input's, clamped at 0; MaxPool: its input's; GELU: min..max of its table with 0 (a refused
+//   element); Embeddings: min..max of its table (a bad token reads row 0); Softmax: min..max of its table with 0 (the index is masked);
+//   IO_ADDC: left * [x] + right * [min w, max w] over the words read; IO_ADD2: left * [x] + right * [y];
+//   model inputs, products, convolutions, LayerNorm, Argmax: unknown.
+// The arithmetic is checked int64: an overflow makes the interval unknown (the device's sums wrap there). A tensor gets a NEW form only when it
+// has none (IQ_NO) and some IO_GEMM whose constant has an int8 copy reads it as in0: IQ_YES within -128..127, IQ_PLANES within -16384..16383,
+// none when the interval is unknown or wider. ReLU and MaxPool write an int8 copy and no planes (infer_q_through): their outputs get IQ_YES or
+// nothing. Every other tensor, and with it the scratch layout and the launches of every program without such a product, stays as it is.
+struct InferRange { bool known = false; int64_t lo = 0, hi = 0; };
+inline InferRange infer_range_axpy(int64_t left, InferRange x, int64_t right, InferRange y) {
+  InferRange r;
+  if (!x.known || !y.known) return r;
+  int64_t a[2], b[2], lo, hi;
+  if (__builtin_mul_overflow(left, x.lo, &a[0]) || __builtin_mul_overflow(left, x.hi, &a[1]) || __builtin_mul_overflow(right, y.lo, &b[0]) || __builtin_mul_overflow(right, y.hi, &b[1])) return r;
+  if (__builtin_add_overflow(std::min(a[0], a[1]), std::min(b[0], b[1]), &lo) || __builtin_add_overflow(std::max(a[0], a[1]), std::max(b[0], b[1]), &hi)) return r;
+  r.known = true; r.lo = lo; r.hi = hi;
+  return r;
+}
+inline std::vector<InferRange> infer_ranges(const InferProgram& p) {
+  std::vector<InferRange> rg(p.tensors.size());
+  auto span = [](const int64_t* w, size_t n, bool with_zero) {
+    InferRange r;
+    if (!w || !n) return r;
+    r.known = true; r.lo = r.hi = with_zero ? 0 : w[0];
+    for (size_t i = 0; i < n; i++) { r.lo = std::min(r.lo, w[i]); r.hi = std::max(r.hi, w[i]); }
+    return r;
+  };
+  for (const InferOp& o : p.ops) {  // (in the order of the ops: every input is written before it is read)
+    const InferRange x = o.in0 >= 0 ? rg[(size_t)o.in0] : InferRange();
+    InferRange r;
+    switch (o.kind) {
+      case IO_REQUANT: r.known = true; r.lo = -127; r.hi = 127; break;
+      case IO_RELU: r = x; r.lo = std::max<int64_t>(r.lo, 0); r.hi = std::max<int64_t>(r.hi, 0); break;
+      case IO_MAXPOOL: r = x; break;
+      case IO_GELU: case IO_SOFTMAX: r = span(p.consts[(size_t)o.table].data(), p.consts[(size_t)o.table].n, true); break;
+      case IO_EMBED: r = span(p.consts[(size_t)o.w].data(), p.consts[(size_t)o.w].n, false); break;
+      case IO_ADDC: r = infer_range_axpy(o.left, x, o.right, span(p.consts[(size_t)o.w].data(), std::min(p.consts[(size_t)o.w].n, p.tensors[(size_t)o.out].len), false)); break;
+      case IO_ADD2: r = infer_range_axpy(o.left, x, o.right, rg[(size_t)o.in1]); break;
+      default: break;
+    }
+    rg[(size_t)o.out] = r;
+  }
+  return rg;
+}
+inline void infer_range_plan(InferProgram& p) {
+  const std::vector<InferRange> rg = infer_ranges(p);
+  std::vector<int> producer(p.tensors.size(), -1);
+  for (const InferOp& o : p.ops) producer[(size_t)o.out] = o.kind;
+  for (const InferOp& o : p.ops) {
+    if (o.kind != IO_GEMM || p.consts[(size_t)o.w].w8.empty()) continue;
+    InferTensor& t = p.tensors[(size_t)o.in0];
+    const InferRange& r = rg[(size_t)o.in0];
+    const int k = producer[(size_t)o.in0];
+    if (t.q != IQ_NO || !r.known) continue;
+    const bool copy = k == IO_RELU || k == IO_MAXPOOL, planes = k == IO_GELU || k == IO_EMBED || k == IO_ADDC || k == IO_ADD2;  // (who writes which form)
+    if ((copy || planes) && r.lo >= -128 && r.hi <= 127) t.q = IQ_YES;
+    else if (planes && r.lo >= -16384 && r.hi <= 16383) t.q = IQ_PLANES;
   }
 }
 struct InferDeviceState;  // the constants on the device (made at the first call, freed with the model)
@@ -446,6 +512,7 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
     const LayerSpec& l = m.layers[(size_t)o.node];
     infer_softmax_shifts(l.kind == L_MHA ? mha_softmax_spec(l) : l, x, nb, shifts, status);
   };
+  infer_range_plan(p);
   infer_fuse_plan(p);
   return p;
 }

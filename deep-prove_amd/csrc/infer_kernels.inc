@@ -1,7 +1,8 @@
 // Kernels and the batch runner of dp_model_infer (infer.h). Included by hip_dev.hip after HipDev; not part of kernels.inc (the SIMT-emulator
 // build of tests/ cuts its kernels from there). Activations are [batch][tensor] int64, with an int8 copy next to every tensor whose values are
 // known to lie within -128..127 (what a Requant writes, and what ReLU / MaxPool make of it): the int8 copies are the operands of k_infer_gemm_i8,
-// k_infer_conv_i8 and k_infer_gemm2_i8. The probabilities of a Softmax (0..4096) have two int8 planes instead, the left operand of k_infer_gemm2_i8.
+// k_infer_conv_i8 and k_infer_gemm2_i8. The probabilities of a Softmax (0..4096) have two int8 planes instead, the left operand of k_infer_gemm2_i8;
+// so has a tensor the planner has bounded within -16384..16383 (infer_range_plan: GELU and Embeddings outputs and sums of such), the left operand of k_infer_gemm_i8_pl.
 // Bad data (a Requant input beyond its bit size, a token outside the vocabulary, ...) refuses its sample: the chunk has one status word per
 // sample, which the five kernels that can refuse data set with a vector atomic to the class (INFER_BAD_* of infer.h) of the first op that refused
 // the sample; the host reads the words with the outputs. Ops run in stream order and the word only ever goes from zero to a class
@@ -28,6 +29,13 @@ __device__ __forceinline__ void infer_flag(bool bad, size_t i, size_t per, unsig
   if (!m) return;
   const unsigned lane = threadIdx.x & 63;
   if (bad && (lane == 0 || !((m >> (lane - 1)) & 1) || i % per == 0)) infer_refuse(status, i / per, cls);
+}
+// The int8 forms of element i of a tensor whose values the planner has bounded (infer_range_plan, the Softmax table scan), beside its int64 form:
+// o8 — the int8 copy (every value within -128..127) — or the two planes lo = v & 127 (0..127) and hi = v >> 7 (arithmetic: -128..127), so that
+// v = 128 * hi + lo exactly for every v of -16384..16383; null pointers: the tensor has no such form in this call
+__device__ __forceinline__ void infer_put_forms(int64_t v, size_t i, int8_t* __restrict__ o8, int8_t* __restrict__ lo, int8_t* __restrict__ hi) {
+  if (o8) o8[i] = (int8_t)v;
+  if (lo) { lo[i] = (int8_t)(v & 127); hi[i] = (int8_t)(v >> 7); }
 }
 // 16 consecutive int8 of row `row` of X[rows][K] from column k on, zeros outside the matrix. K % 16 == 0: one aligned 16-byte load
 __device__ __forceinline__ infer_v4i infer_ld16(const int8_t* __restrict__ X, size_t rows, size_t K, size_t row, size_t k, bool k16) {
@@ -310,26 +318,143 @@ template <bool RELU, bool W64> __global__ __launch_bounds__(256) void k_infer_ge
     }
   }
 }
-// Add with a static operand / Positional::Learned: left * x + right * w[i mod len] (w: the operand, or the first rows of the table)
-__global__ __launch_bounds__(256) void k_infer_addc(const int64_t* __restrict__ x, const int64_t* __restrict__ w, int64_t* __restrict__ o, size_t n, size_t len, int64_t left, int64_t right) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) o[i] = (int64_t)((uint64_t)left * (uint64_t)x[i] + (uint64_t)right * (uint64_t)w[i % len]);
+// The constant product on a TWO-PLANE left operand (IQ_PLANES: values within -16384..16383 as lo = v & 127 and hi = v >> 7, v = 128 * hi + lo):
+// C = (128 * Ahi + Alo)[M][K] * Bt[N][K]^T + bias[N], exact — each plane is an int8 matrix, so each of the two 32-bit accumulators keeps the
+// bound K * 128 * 128 < 2^31 of weight_const, and v = 128 * (int64)acc_hi + acc_lo + bias is formed in 64 bits. Served in both shapes of the
+// launcher: RQ = false is the contract of k_infer_gemm_i8 (the int64 result to O64), RQ = true that of k_infer_gemm_i8_rq (bias + Requant
+// (+ ReLU: RELU), O8 always, O64 under W64, refusal through infer_refuse with INFER_BAD_REQUANT), its epilogue letter for letter on v.
+// One launch, not one per plane: a workgroup (4 waves, 64 x 64 tile, 32 x 32 per wave) stages BOTH planes of its A slice and ONE Bt slice through
+//   LDS; a wave holds two accumulators and issues two v_mfma_i32_32x32x32_i8 per Bt fragment — three LDS fragment reads per two MFMA where the
+//   one-plane kernels do two per MFMA, and Bt (the operand every row tile re-reads) crosses global memory and LDS once, not twice.
+// Staging: K slices of PL_TK = 128 at row pitch PL_LD, the NEXT slice's 6 x 16 bytes per thread prefetched into registers right behind the
+//   barrier that publishes the current one (k_infer_gemm_i8_rq's scheme with a third operand). LDS: (2 * 64 + 64) * 144 = 27648 bytes, five
+//   workgroups per CU; a slice of 64 would double the barriers per MFMA for an LDS the 32 accumulator registers do not let more waves use.
+//   The result tile of the fused shape lies in the operand buffers behind a barrier, [64][RQ_LDC] bytes.
+// Fragments: as k_infer_gemm_i8 — lane l holds 16 consecutive k (16 * (l >> 5) ...) of row l & 31 of both planes of A and of column l & 31 of B,
+//   the SAME (lane half, byte) -> k rule for the three. Rows >= M, columns >= N and k >= K are zero-filled in registers before they reach LDS
+//   (infer_ld16; nothing is read past a matrix) and are never tested, stored or flagged; MFMA steps beyond K are skipped.
+constexpr int PL_TK = 128, PL_LD = PL_TK + 16;
+template <bool RQ, bool RELU, bool W64> __global__ __launch_bounds__(256) void k_infer_gemm_i8_pl(const int8_t* __restrict__ Alo, const int8_t* __restrict__ Ahi, const int8_t* __restrict__ Bt, const int64_t* __restrict__ bias,
+                                                                                               int8_t* __restrict__ O8, int64_t* __restrict__ O64, size_t M, size_t K, size_t N, int64_t mult, unsigned sh, unsigned bits,
+                                                                                               unsigned* status, size_t R) {
+  __shared__ __attribute__((aligned(16))) int8_t lds[(2 * IG_TM + IG_TN) * PL_LD];
+  int8_t* Al = lds; int8_t* Ah = lds + IG_TM * PL_LD; int8_t* Bs = lds + 2 * IG_TM * PL_LD; int8_t* Cs = lds;  // (Cs: [IG_TM][RQ_LDC], after the last slice)
+  static_assert(IG_TM * RQ_LDC <= (2 * IG_TM + IG_TN) * PL_LD && IG_TM == 64 && IG_TN == 64 && PL_TK % 32 == 0, "the result tile lies in the operand buffers");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t m0 = (size_t)blockIdx.x * IG_TM, n0 = (size_t)blockIdx.y * IG_TN;
+  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
+  const int lr = tid >> 3, lc = (tid & 7) * 16;  // the bytes of a slice this thread stages: tile rows lr and lr + 32, byte column lc
+  const bool k16 = (K & 15) == 0;
+  infer_v16i acc, acc2;  // lo plane, hi plane
+#pragma unroll
+  for (int r = 0; r < 16; r++) acc[r] = acc2[r] = 0;
+  infer_v4i l0 = infer_ld16(Alo, M, K, m0 + lr, lc, k16), l1 = infer_ld16(Alo, M, K, m0 + lr + 32, lc, k16);
+  infer_v4i h0 = infer_ld16(Ahi, M, K, m0 + lr, lc, k16), h1 = infer_ld16(Ahi, M, K, m0 + lr + 32, lc, k16);
+  infer_v4i b0 = infer_ld16(Bt, N, K, n0 + lr, lc, k16), b1 = infer_ld16(Bt, N, K, n0 + lr + 32, lc, k16);
+  for (size_t k0 = 0; k0 < K; k0 += PL_TK) {
+    __syncthreads();  // (the fragments of the slice before have been read)
+    *(infer_v4i*)&Al[lr * PL_LD + lc] = l0; *(infer_v4i*)&Al[(lr + 32) * PL_LD + lc] = l1;
+    *(infer_v4i*)&Ah[lr * PL_LD + lc] = h0; *(infer_v4i*)&Ah[(lr + 32) * PL_LD + lc] = h1;
+    *(infer_v4i*)&Bs[lr * PL_LD + lc] = b0; *(infer_v4i*)&Bs[(lr + 32) * PL_LD + lc] = b1;
+    __syncthreads();
+    const size_t kn = k0 + PL_TK + lc;  // the next slice: zeros, and no load, at kn >= K
+    l0 = infer_ld16(Alo, M, K, m0 + lr, kn, k16); l1 = infer_ld16(Alo, M, K, m0 + lr + 32, kn, k16);
+    h0 = infer_ld16(Ahi, M, K, m0 + lr, kn, k16); h1 = infer_ld16(Ahi, M, K, m0 + lr + 32, kn, k16);
+    b0 = infer_ld16(Bt, N, K, n0 + lr, kn, k16); b1 = infer_ld16(Bt, N, K, n0 + lr + 32, kn, k16);
+#pragma unroll
+    for (int s = 0; s < PL_TK / 32; s++) {
+      if (k0 + s * 32 < K) {  // (uniform)
+        const int at = (wm + (lane & 31)) * PL_LD + s * 32 + (lane >> 5) * 16;
+        const infer_v4i fb = *(const infer_v4i*)&Bs[(wn + (lane & 31)) * PL_LD + s * 32 + (lane >> 5) * 16];
+        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(*(const infer_v4i*)&Al[at], fb, acc, 0, 0, 0);
+        acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(*(const infer_v4i*)&Ah[at], fb, acc2, 0, 0, 0);
+      }
+    }
+  }
+  const size_t col = n0 + wn + (lane & 31);
+  const uint64_t bv = bias && col < N ? (uint64_t)bias[col] : 0;
+  if (!RQ) {  // the contract of k_infer_gemm_i8
+    if (col >= N) return;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+      const size_t row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      if (row < M) O64[row * N + col] = (int64_t)((uint64_t)((int64_t)acc2[r] * 128 + (int64_t)acc[r]) + bv);
+    }
+    return;
+  }
+  __syncthreads();  // (every wave has read its last fragments: the operand buffers become the result tile)
+  const uint64_t lim = uint64_t(1) << bits;
+  unsigned bad = 0;
+#pragma unroll
+  for (int r = 0; r < 16; r++) {
+    const int tr = wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    const int64_t v = (int64_t)((uint64_t)((int64_t)acc2[r] * 128 + (int64_t)acc[r]) + bv);
+    const uint64_t mag = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
+    if (mag > lim && m0 + tr < M && col < N) bad |= 1u << r;
+    int64_t y = (int64_t)((uint64_t)v * (uint64_t)mult + (uint64_t(1) << (sh - 1))) >> sh;
+    y = y < -127 ? -127 : y > 127 ? 127 : y;
+    if (RELU) y = y < 0 ? 0 : y;
+    Cs[tr * RQ_LDC + wn + (lane & 31)] = (int8_t)y;
+  }
+  if (__ballot(bad != 0)) {
+#pragma unroll
+    for (int r = 0; r < 16; r++) if ((bad >> r) & 1) infer_refuse(status, (m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) / R, INFER_BAD_REQUANT);
+  }
+  __syncthreads();
+  if ((N & 15) == 0) {  // one 16-byte vector of a row per thread
+    const size_t row = m0 + (tid >> 2), c = n0 + (tid & 3) * 16;
+    if (row < M && c < N) *(infer_v4i*)(O8 + row * N + c) = *(const infer_v4i*)&Cs[(tid >> 2) * RQ_LDC + (tid & 3) * 16];
+  } else {
+    for (int i = tid; i < IG_TM * IG_TN; i += 256) {
+      const size_t row = m0 + (i >> 6), c = n0 + (i & 63);
+      if (row < M && c < N) O8[row * N + c] = Cs[(i >> 6) * RQ_LDC + (i & 63)];
+    }
+  }
+  if (!W64) return;
+  if ((N & 1) == 0) {  // (the int64 form of a tensor starts 256-aligned: an even column of any row is 16-aligned)
+    for (int i = tid; i < IG_TM * IG_TN / 2; i += 256) {
+      const size_t row = m0 + (i >> 5), c = n0 + (i & 31) * 2;
+      const int8_t* y = &Cs[(i >> 5) * RQ_LDC + (i & 31) * 2];
+      if (row < M && c < N) { infer_v2l v; v[0] = y[0]; v[1] = y[1]; *(infer_v2l*)(O64 + row * N + c) = v; }
+    }
+  } else {
+    for (int i = tid; i < IG_TM * IG_TN; i += 256) {
+      const size_t row = m0 + (i >> 6), c = n0 + (i & 63);
+      if (row < M && c < N) O64[row * N + c] = Cs[(i >> 6) * RQ_LDC + (i & 63)];
+    }
+  }
 }
-__global__ __launch_bounds__(256) void k_infer_add2(const int64_t* __restrict__ x, const int64_t* __restrict__ y, int64_t* __restrict__ o, size_t n, int64_t left, int64_t right) {
+// Add with a static operand / Positional::Learned: left * x + right * w[i mod len] (w: the operand, or the first rows of the table).
+// o8 / lo, hi (here and in k_infer_add2, k_infer_embed, k_infer_gelu): the int8 forms of the output, infer_put_forms
+__global__ __launch_bounds__(256) void k_infer_addc(const int64_t* __restrict__ x, const int64_t* __restrict__ w, int64_t* __restrict__ o, int8_t* __restrict__ o8, int8_t* __restrict__ lo, int8_t* __restrict__ hi,
+                                                    size_t n, size_t len, int64_t left, int64_t right) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) o[i] = (int64_t)((uint64_t)left * (uint64_t)x[i] + (uint64_t)right * (uint64_t)y[i]);
+  if (i >= n) return;
+  const int64_t v = (int64_t)((uint64_t)left * (uint64_t)x[i] + (uint64_t)right * (uint64_t)w[i % len]);
+  o[i] = v;
+  infer_put_forms(v, i, o8, lo, hi);
+}
+__global__ __launch_bounds__(256) void k_infer_add2(const int64_t* __restrict__ x, const int64_t* __restrict__ y, int64_t* __restrict__ o, int8_t* __restrict__ o8, int8_t* __restrict__ lo, int8_t* __restrict__ hi,
+                                                    size_t n, int64_t left, int64_t right) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t v = (int64_t)((uint64_t)left * (uint64_t)x[i] + (uint64_t)right * (uint64_t)y[i]);
+  o[i] = v;
+  infer_put_forms(v, i, o8, lo, hi);
 }
 // Embeddings: row tok[t] of the [vocab][emb] table for every token; a token outside the vocabulary refuses the sample (per = output words per
 // sample) and reads row 0: the table is never read outside its rows, whatever the token
-__global__ __launch_bounds__(256) void k_infer_embed(const int64_t* __restrict__ tok, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n, size_t vocab, size_t emb,
-                                                     unsigned* status, size_t per) {
+__global__ __launch_bounds__(256) void k_infer_embed(const int64_t* __restrict__ tok, const int64_t* __restrict__ table, int64_t* __restrict__ o, int8_t* __restrict__ o8, int8_t* __restrict__ lo, int8_t* __restrict__ hi,
+                                                     size_t n, size_t vocab, size_t emb, unsigned* status, size_t per) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int64_t t = tok[i / emb];
   const bool bad = t < 0 || (uint64_t)t >= vocab;
   infer_flag(bad, i, per, status, INFER_BAD_TOKEN);
   if (bad) t = 0;
-  o[i] = table[(size_t)t * emb + i % emb];
+  const int64_t v = table[(size_t)t * emb + i % emb];
+  o[i] = v;
+  infer_put_forms(v, i, o8, lo, hi);
 }
 // MaxPool 2 x 2, stride 2, on [batch][c][h][w]
 __global__ __launch_bounds__(256) void k_infer_maxpool(const int64_t* __restrict__ x, int64_t* __restrict__ o, int8_t* __restrict__ o8, size_t n, size_t h, size_t w) {
@@ -438,17 +563,19 @@ template <int RN> __global__ __launch_bounds__(256) void k_infer_conv_i8(const i
   }
 }
 // Activation::Gelu (gelu_op): table[v * mult + max], the table's rows being -max .. max - 1. |v| > 2^20 or a scaled value outside the table
-// refuses the sample (per = words per sample) and nothing is read: the same test guards the table against the values of a sample refused earlier
-__global__ __launch_bounds__(256) void k_infer_gelu(const int64_t* __restrict__ x, const int64_t* __restrict__ table, int64_t* __restrict__ o, size_t n, int64_t mult, int64_t mx,
-                                                    unsigned* status, size_t per) {
+// refuses the sample (per = words per sample) and nothing is read: the same test guards the table against the values of a sample refused earlier.
+// The zero of a refused element goes to the int8 forms like any table entry (the planner's interval of the tensor includes 0)
+__global__ __launch_bounds__(256) void k_infer_gelu(const int64_t* __restrict__ x, const int64_t* __restrict__ table, int64_t* __restrict__ o, int8_t* __restrict__ o8, int8_t* __restrict__ lo, int8_t* __restrict__ hi,
+                                                    size_t n, int64_t mult, int64_t mx, unsigned* status, size_t per) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t v = x[i], lim = int64_t(1) << 20;
   const int64_t scaled = (int64_t)((uint64_t)v * (uint64_t)mult);  // (|v| <= 2^20 and mult <= 2^12 once the first check holds)
   const bool bad = v < -lim || v > lim || scaled < -mx || scaled >= mx;
   infer_flag(bad, i, per, status, INFER_BAD_GELU);
-  if (bad) { o[i] = 0; return; }
-  o[i] = table[scaled + mx];
+  const int64_t y = bad ? 0 : table[scaled + mx];
+  o[i] = y;
+  infer_put_forms(y, i, o8, lo, hi);
 }
 __device__ __forceinline__ uint64_t infer_wave_sum(uint64_t v) {
 #pragma unroll
@@ -502,7 +629,7 @@ __global__ __launch_bounds__(256) void k_infer_softmax(const int64_t* __restrict
   r >>= tv;
   for (unsigned z = 0; z < zc; z++) { acc *= (r & ((int64_t(1) << zv) - 1)) == 0 ? 1 : 0; r >>= zv; }
   o[i] = acc;
-  if (lo) { lo[i] = (int8_t)(acc & 127); hi[i] = (int8_t)(acc >> 7); }  // (the planner has seen every table entry within 0..16383)
+  infer_put_forms(acc, i, nullptr, lo, hi);  // (the planner has seen every table entry within 0..16383)
 }
 // Logits::Argmax (argmax_rows): one wave per row of K words (rows counts samples x rows of a sample); lanes stride over the row and keep (value,
 // index) under "greater, or equal at a smaller index"; the pairs are reduced across the wave by the same rule, so the result is the FIRST maximum
@@ -660,6 +787,7 @@ static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferS
       if (i8) {
         const size_t M = nb * o.g.R;
         const dim3 grid((unsigned)((M + IG_TM - 1) / IG_TM), (unsigned)((o.g.N + IG_TN - 1) / IG_TN));
+        const bool pl = m.q[(size_t)o.in0] == IQ_PLANES;  // a two-plane input: k_infer_gemm_i8_pl in either shape, counted as the one-plane launches are
         launches[IO_KINDS + 2]++;
         if (fuse && o.d[0]) {
           const InferOp& rq = p.ops[o.d[1]];
@@ -667,12 +795,17 @@ static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferS
           const int last = relu ? p.ops[o.d[2]].out : rq.out;
           int64_t* o64 = infer_needs_int64(p, last, m.q, nb, no_mfma) ? m.T64(last) : nullptr;
           auto go = [&](auto kern) { kern<<<grid, 256, 0, s>>>(m.T8(o.in0), infer_const8(p, st, o.w), c64(o.bias), m.T8(last), o64, M, o.g.K, o.g.N, rq.left, rq.shift, rq.bits, m.status(), o.g.R); };
-          if (relu) { if (o64) go(k_infer_gemm_i8_rq<true, true>); else go(k_infer_gemm_i8_rq<true, false>); }
+          auto go_pl = [&](auto kern) { kern<<<grid, 256, 0, s>>>(m.TP(o.in0, 0), m.TP(o.in0, 1), infer_const8(p, st, o.w), c64(o.bias), m.T8(last), o64, M, o.g.K, o.g.N, rq.left, rq.shift, rq.bits, m.status(), o.g.R); };
+          if (pl) {
+            if (relu) { if (o64) go_pl(k_infer_gemm_i8_pl<true, true, true>); else go_pl(k_infer_gemm_i8_pl<true, true, false>); }
+            else { if (o64) go_pl(k_infer_gemm_i8_pl<true, false, true>); else go_pl(k_infer_gemm_i8_pl<true, false, false>); }
+          } else if (relu) { if (o64) go(k_infer_gemm_i8_rq<true, true>); else go(k_infer_gemm_i8_rq<true, false>); }
           else { if (o64) go(k_infer_gemm_i8_rq<false, true>); else go(k_infer_gemm_i8_rq<false, false>); }
           launches[IO_REQUANT]++; launches[IO_RELU] += relu; launches[IO_KINDS + 5]++; launches[IO_KINDS + 6] += o.d[0];
           return o.d[0];
         }
-        k_infer_gemm_i8<<<grid, 256, 0, s>>>(m.T8(o.in0), infer_const8(p, st, o.w), c64(o.bias), m.T64(o.out), M, o.g.K, o.g.N);
+        if (pl) k_infer_gemm_i8_pl<false, false, true><<<grid, 256, 0, s>>>(m.TP(o.in0, 0), m.TP(o.in0, 1), infer_const8(p, st, o.w), c64(o.bias), nullptr, m.T64(o.out), M, o.g.K, o.g.N, 0, 1, 0, nullptr, o.g.R);
+        else k_infer_gemm_i8<<<grid, 256, 0, s>>>(m.T8(o.in0), infer_const8(p, st, o.w), c64(o.bias), m.T64(o.out), M, o.g.K, o.g.N);
       } else k_infer_gemm_i64<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), p.tensors[(size_t)o.in0].len, c64(o.w), 0, c64(o.bias), m.T64(o.out), len, nb, o.g);
       break;
     case IO_GEMM2: {
@@ -689,9 +822,9 @@ static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferS
     }
     case IO_REQUANT: k_infer_requant<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.out), m.T8(o.out), n, o.left, o.shift, o.bits, m.status(), len); break;
     case IO_RELU: k_infer_relu<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.out), m.T8(o.out), n); break;
-    case IO_ADDC: k_infer_addc<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), m.T64(o.out), n, len, o.left, o.right); break;
-    case IO_ADD2: k_infer_add2<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.in1), m.T64(o.out), n, o.left, o.right); break;
-    case IO_EMBED: k_infer_embed<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), m.T64(o.out), n, o.d[0], o.d[1], m.status(), len); break;
+    case IO_ADDC: k_infer_addc<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), m.T64(o.out), m.T8(o.out), m.TP(o.out, 0), m.TP(o.out, 1), n, len, o.left, o.right); break;
+    case IO_ADD2: k_infer_add2<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.in1), m.T64(o.out), m.T8(o.out), m.TP(o.out, 0), m.TP(o.out, 1), n, o.left, o.right); break;
+    case IO_EMBED: k_infer_embed<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), m.T64(o.out), m.T8(o.out), m.TP(o.out, 0), m.TP(o.out, 1), n, o.d[0], o.d[1], m.status(), len); break;
     case IO_MAXPOOL: k_infer_maxpool<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.out), m.T8(o.out), n, o.d[1], o.d[2]); break;
     case IO_CONV:
       if (i8) {  // (the planner made the image: rn is 4 or 8 and the LDS fits)
@@ -707,7 +840,7 @@ static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferS
         launches[IO_KINDS + 3]++;
       } else k_infer_conv<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), c64(o.bias), m.T64(o.out), n, o.d[0], o.d[1], o.d[2], o.d[3], o.d[4], o.d[5], o.d[6]);
       break;
-    case IO_GELU: k_infer_gelu<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.table), m.T64(o.out), n, o.left, (int64_t)o.d[0], m.status(), len); break;
+    case IO_GELU: k_infer_gelu<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.table), m.T64(o.out), m.T8(o.out), m.TP(o.out, 0), m.TP(o.out, 1), n, o.left, (int64_t)o.d[0], m.status(), len); break;
     case IO_LAYERNORM: {
       const size_t rows = n / o.d[0];
       k_infer_layernorm<<<infer_grid(rows * 64), 256, 0, s>>>(m.T64(o.in0), c64(o.w), c64(o.bias), c64(o.table), m.T64(o.out), rows, o.d[0], (int64_t)o.d[1], o.left, o.shift, m.status(), len / o.d[0]);
