@@ -72,6 +72,9 @@ struct InferOp {
   // IO_GEMM2: d[0] = infer_gemm2_plan (IG2_*; 0: the op stays on k_infer_gemm_i64); IO_GEMM: d[0] = the ops behind it that k_infer_gemm_i8_rq
   // absorbs (infer_fuse_plan: 0 none, 1 its Requant, 2 the Requant and a ReLU), d[1], d[2] = their indices in InferProgram::ops
   size_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // IO_CONV: the ops behind it that the epilogue of k_infer_conv_i8_rq absorbs (infer_fuse_plan), as indices in InferProgram::ops in chain
+  // order: its Requant, then a ReLU and / or a MaxPool; nfused = 0: none
+  int nfused = 0, fused[3] = {-1, -1, -1};
 };
 // k_infer_conv_i8 (infer_kernels.inc): a workgroup computes IC_TC output channels of a strip of IC_TP consecutive pixels of one sample's plane; the
 // filter tile goes through LDS in K slices of IC_TK bytes (row pitch IC_LDA). Its dynamic LDS, in this order: the filter slice, one word per
@@ -141,6 +144,10 @@ inline bool infer_needs_int64(const InferProgram& p, int t, const std::vector<ch
 // in the order of the ops, so no op in between may be one that refuses data under another class (Embeddings, GELU, LayerNorm, Softmax): the
 // status word holds the class of the FIRST op that refused a sample. Whether the head's input has its int8 form, and whether the chain's last
 // tensor still needs its int64 form, is known per call only (infer_launch).
+// The chains k_infer_conv_i8_rq serves, under the same rules (InferOp::fused): an IO_CONV that has its int8 image, its Requant with shift >= 1,
+// then optionally a ReLU, then optionally — behind the ReLU or straight behind the Requant — a MaxPool. The MaxPool is absorbed only where a
+// strip of IC_TP pixels holds whole pairs of rows (nw <= 64 and a divisor of IC_TP) and its (c, h, w) are the conv's (kw, nw, nw); otherwise the
+// chain ends in front of it and k_infer_maxpool runs.
 inline void infer_fuse_plan(InferProgram& p) {
   const size_t nt = p.tensors.size(), no = p.ops.size();
   std::vector<int> readers(nt, 0), reader(nt, -1);
@@ -155,6 +162,17 @@ inline void infer_fuse_plan(InferProgram& p) {
   };
   for (size_t i = 0; i < no; i++) {
     InferOp& o = p.ops[i];
+    if (o.kind == IO_CONV && o.d[7]) {  // (o.d[7]: the conv has its int8 image)
+      const int rq = sole(o.out, IO_REQUANT, i);
+      if (rq < 0 || p.ops[(size_t)rq].shift < 1) continue;
+      o.fused[o.nfused++] = rq;
+      const int rl = sole(p.ops[(size_t)rq].out, IO_RELU, i);
+      if (rl >= 0) o.fused[o.nfused++] = rl;
+      const int mp = sole(p.ops[(size_t)(rl < 0 ? rq : rl)].out, IO_MAXPOOL, i);
+      const size_t kw = o.d[0], nw = o.d[3];
+      if (mp >= 0 && nw <= 64 && IC_TP % nw == 0 && p.ops[(size_t)mp].d[0] == kw && p.ops[(size_t)mp].d[1] == nw && p.ops[(size_t)mp].d[2] == nw) o.fused[o.nfused++] = mp;
+      continue;
+    }
     if (o.kind != IO_GEMM || p.consts[(size_t)o.w].w8.empty()) continue;
     const int rq = sole(o.out, IO_REQUANT, i);
     if (rq < 0 || p.ops[(size_t)rq].shift < 1) continue;

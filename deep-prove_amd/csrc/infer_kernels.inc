@@ -495,6 +495,37 @@ template <int RN> __device__ __forceinline__ infer_v4i infer_conv_frag(const uns
   }
   return v;
 }
+// The staging and the MFMA loop of a live workgroup of k_infer_conv_i8 / k_infer_conv_i8_rq (described at the former): the row table and the kx
+// spans go to LDS once, the filter tile in K slices of IC_TK; acc += the 32 channels x 32 pixels of the wave. Called by every thread of the
+// workgroup (it holds barriers); the last fragments of As may still be read by another wave when it returns
+template <int RN> __device__ __forceinline__ void infer_conv_tile(infer_v16i& acc, const int8_t* __restrict__ x, const int8_t* __restrict__ f, int8_t* As, unsigned* tab, unsigned* xs, unsigned b, unsigned p0,
+                                                                  unsigned ch0, unsigned tid, unsigned half, unsigned l31, unsigned pl, bool wave_live, unsigned kw, unsigned kx, unsigned ra, unsigned K,
+                                                                  unsigned nw) {
+  const unsigned nn = nw * nw, pw = infer_conv_pitch(nw, ra, RN) / 4;  // (the pitch of a span in words)
+  for (unsigned q = tid; q < K / RN; q += 256) tab[q] = q < kx * ra ? q / ra * pw + q % ra * (nw / 4) : 0;
+  for (unsigned i = tid; i < kx * pw; i += 256) {
+    const unsigned j = i / pw, at = p0 + 4 * (i % pw);
+    xs[i] = at < nn ? *(const unsigned*)(x + ((size_t)b * kx + j) * nn + at) : 0u;
+  }
+  const unsigned lr = tid >> 3, lc = (tid & 7) * 16;  // the 16 bytes of the filter slice this thread stages: tile row, byte column
+  for (unsigned k0 = 0; k0 < K; k0 += IC_TK) {
+    infer_v4i a = {0, 0, 0, 0};
+    if (ch0 + lr < kw && k0 + lc < K) a = *(const infer_v4i*)(f + (size_t)(ch0 + lr) * K + k0 + lc);
+    __syncthreads();  // (the fragments of the slice before have been read)
+    *(infer_v4i*)&As[lr * IC_LDA + lc] = a;
+    __syncthreads();  // (the first one: the spans and the table are in LDS, too)
+    if (wave_live) {
+#pragma unroll
+      for (unsigned s = 0; s < IC_TK / 32; s++) {
+        if (k0 + s * 32 < K) {
+          const infer_v4i fa = *(const infer_v4i*)&As[l31 * IC_LDA + s * 32 + half * 16];
+          const infer_v4i fb = infer_conv_frag<RN>(xs, tab, (k0 + s * 32 + half * 16) / RN, pl >> 2, pl & 3);
+          acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa, fb, acc, 0, 0, 0);
+        }
+      }
+    }
+  }
+}
 // k_infer_conv on the i8 MFMA, exact: out[b][ch][p] = bias[ch] + sum over (j, a, c) of x[b][j][p + a * nw + c] * f[ch][j][a][c] on the flat plane
 // index p < nn = nw * nw, then clear_garbage. x: the int8 copy of the input, [batch][kx][nn]; f: the packed filter image [kw][K] of
 // infer_conv_pack, k = (j * ra + a) * RN + c (RN = the padded kernel side, 4 or 8; K a multiple of 32 with K * 128 * 128 < 2^31).
@@ -520,7 +551,7 @@ template <int RN> __global__ __launch_bounds__(256) void k_infer_conv_i8(const i
   unsigned* tab = (unsigned*)(ic_lds + IC_TC * IC_LDA);
   unsigned* xs = tab + infer_conv_tab_words(K, RN);
   const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
-  const unsigned nn = nw * nw, pw = infer_conv_pitch(nw, ra, RN) / 4;  // (the pitch of a span in words)
+  const unsigned nn = nw * nw;
   const unsigned b = blockIdx.x / strips, p0 = (blockIdx.x % strips) * IC_TP, ch0 = blockIdx.y * IC_TC;
   const unsigned pl = wave * 32 + l31, p = p0 + pl;
   const bool tile_live = ch0 < u0 && p0 / nw < u1;                                         // (uniform in the workgroup)
@@ -528,31 +559,7 @@ template <int RN> __global__ __launch_bounds__(256) void k_infer_conv_i8(const i
   infer_v16i acc;
 #pragma unroll
   for (int r = 0; r < 16; r++) acc[r] = 0;
-  if (tile_live) {
-    for (unsigned q = tid; q < K / RN; q += 256) tab[q] = q < kx * ra ? q / ra * pw + q % ra * (nw / 4) : 0;
-    for (unsigned i = tid; i < kx * pw; i += 256) {
-      const unsigned j = i / pw, at = p0 + 4 * (i % pw);
-      xs[i] = at < nn ? *(const unsigned*)(x + ((size_t)b * kx + j) * nn + at) : 0u;
-    }
-    const unsigned lr = tid >> 3, lc = (tid & 7) * 16;  // the 16 bytes of the filter slice this thread stages: tile row, byte column
-    for (unsigned k0 = 0; k0 < K; k0 += IC_TK) {
-      infer_v4i a = {0, 0, 0, 0};
-      if (ch0 + lr < kw && k0 + lc < K) a = *(const infer_v4i*)(f + (size_t)(ch0 + lr) * K + k0 + lc);
-      __syncthreads();  // (the fragments of the slice before have been read)
-      *(infer_v4i*)&As[lr * IC_LDA + lc] = a;
-      __syncthreads();  // (the first one: the spans and the table are in LDS, too)
-      if (wave_live) {
-#pragma unroll
-        for (unsigned s = 0; s < IC_TK / 32; s++) {
-          if (k0 + s * 32 < K) {
-            const infer_v4i fa = *(const infer_v4i*)&As[l31 * IC_LDA + s * 32 + half * 16];
-            const infer_v4i fb = infer_conv_frag<RN>(xs, tab, (k0 + s * 32 + half * 16) / RN, pl >> 2, pl & 3);
-            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa, fb, acc, 0, 0, 0);
-          }
-        }
-      }
-    }
-  }
+  if (tile_live) infer_conv_tile<RN>(acc, x, f, As, tab, xs, b, p0, ch0, tid, half, l31, pl, wave_live, kw, kx, ra, K, nw);
   if (p >= nn) return;
   const bool keep = wave_live && p / nw < u1 && p % nw < u2;
   int64_t* op = o + (size_t)b * kw * nn + p;
@@ -560,6 +567,118 @@ template <int RN> __global__ __launch_bounds__(256) void k_infer_conv_i8(const i
   for (int r = 0; r < 16; r++) {
     const unsigned ch = ch0 + (r & 3) + 8 * (r >> 2) + 4 * half;
     if (ch < kw) op[(size_t)ch * nn] = keep && ch < u0 ? (int64_t)acc[r] + bias[ch] : (int64_t)0;
+  }
+}
+// MaxPool 2 x 2 stride 2 (k_infer_maxpool's rule) on one channel row of the result tile of k_infer_conv_i8_rq: `row` holds whole pairs of rows of
+// a plane of side nw. infer_pool1: pooled pixel j of the strip. infer_pool4: the four pooled pixels j .. j + 3, byte t = pixel j + t, for
+// j % 4 == 0 and nw % 8 == 0 — they share a pooled row and their 2 x 8 tile bytes are two aligned 8-byte words (the tile's pitch is a multiple of 16)
+__device__ __forceinline__ int infer_pool1(const int8_t* row, unsigned j, unsigned nw) {
+  const int8_t* q = row + 2 * (j / (nw / 2)) * nw + 2 * (j % (nw / 2));
+  const int a = q[0] > q[1] ? q[0] : q[1], b = q[nw] > q[nw + 1] ? q[nw] : q[nw + 1];
+  return a > b ? a : b;
+}
+__device__ __forceinline__ unsigned infer_pool4(const int8_t* row, unsigned j, unsigned nw) {
+  const unsigned at = 2 * (j / (nw / 2)) * nw + 2 * (j % (nw / 2));
+  const uint2 a = *(const uint2*)(row + at), b = *(const uint2*)(row + at + nw);
+  unsigned w = 0;
+#pragma unroll
+  for (int t = 0; t < 4; t++) {
+    const unsigned ua = t < 2 ? a.x : a.y, ub = t < 2 ? b.x : b.y, s = 16 * (t & 1);
+    const int m0 = (int8_t)(ua >> s), m1 = (int8_t)(ua >> (s + 8)), m2 = (int8_t)(ub >> s), m3 = (int8_t)(ub >> (s + 8));
+    const int ma = m0 > m1 ? m0 : m1, mb = m2 > m3 ? m2 : m3;
+    w |= (unsigned)((ma > mb ? ma : mb) & 255) << (8 * t);
+  }
+  return w;
+}
+// A convolution with the Requant behind it, a ReLU behind that (RELU) and a MaxPool behind either (POOL) in ONE launch (infer_fuse_plan): the
+// staging and the MFMA loop of k_infer_conv_i8 (infer_conv_tile: same grid, same LDS, a workgroup of 4 waves owns IC_TC = 32 channels x IC_TP = 128
+// consecutive pixels of the plane of sample blockIdx.x / strips; lane = pixel, register r of a lane = channel (r & 3) + 8 * (r >> 2) +
+// 4 * (lane >> 5)), then in registers, per element:
+//   v = keep && ch < u0 ? acc + bias[ch] : 0 — what k_infer_conv_i8 stores: clear_garbage first, a cleared element is 0 —, then what
+//   k_infer_requant does, letter for letter (the epilogue of k_infer_gemm_i8_rq): |v| > 2^bits refuses the sample, (v * mult + 2^(sh-1)) >> sh with
+//   the multiply and add in unsigned 64-bit arithmetic and an arithmetic shift, clamp to +-127; then max(., 0) under RELU.
+// Refusal: a workgroup holds one sample. A lane ORs its 16 tests into a mask; ONE ballot per wave decides, and only the lanes of a wave with a bad
+//   element call infer_refuse (INFER_BAD_REQUANT). Elements at ch >= kw or p >= nn are never tested, stored or flagged.
+// Result tile: the int8 values go to LDS as [32 channels][128 pixels] at row pitch IC_LDA, into the filter-slice buffer As — IC_TC * IC_LDA bytes,
+//   exactly this tile, free behind one barrier after the last slice. A dead workgroup (all channels >= u0 or all rows >= u1) stages nothing and
+//   its tile is zeros, as are the pixels >= nn of a plane shorter than a strip. After a second barrier every thread reads what others wrote:
+//   no POOL: O8[b][ch][nn] leaves as 16-byte vectors along the pixels, 8 per channel row, one per thread (the int8 copy of a tensor starts
+//     256-aligned, p0 is a multiple of 128 and nn of 16: a vector at p0 + 16 i < nn is aligned and ends within the plane);
+//   POOL: the strip is 128 / nw whole rows from an even row on, or the whole plane (nn < 128) — whole pairs of rows for every nw the planner
+//     admits —, min(128, nn) / 4 pooled pixels per channel, contiguous in O8[b][ch][nn / 4] from p0 / 4 on: 16-byte vectors (infer_pool4) where
+//     that count is a multiple of 16 (then nw % 8 == 0), bytes otherwise. The max runs over requantised, ReLU'd, cleared values: the integers of
+//     the three separate kernels. Neither the conv's tensor nor the Requant's or the ReLU's is written;
+//   W64: the int64 form of the chain's LAST tensor (infer_needs_int64) from the same tile, sign-extended, in 16-byte pairs (an even element of
+//     a channel row is 16-aligned: the int64 form starts 256-aligned and nn, nn / 4, p0 and p0 / 4 are even).
+// In bounds: as k_infer_conv_i8 for the loads; bias[ch] at ch < u0 <= kw; LDS within the tile (rows < 32, pixels < 128; a pooled pixel j <
+//   min(128, nn) / 4 reads rows 2 pr and 2 pr + 1 < min(128, nn) / nw); stores at ch < kw and p < nn (pooled: p0 / 4 + j < nn / 4).
+template <int RN, bool RELU, bool POOL, bool W64> __global__ __launch_bounds__(256) void k_infer_conv_i8_rq(const int8_t* __restrict__ x, const int8_t* __restrict__ f, const int64_t* __restrict__ bias,
+    int8_t* __restrict__ O8, int64_t* __restrict__ O64, unsigned strips, unsigned kw, unsigned kx, unsigned ra, unsigned K, unsigned nw, unsigned u0, unsigned u1, unsigned u2, int64_t mult, unsigned sh,
+    unsigned bits, unsigned* status) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ic_lds[];
+  int8_t* As = (int8_t*)ic_lds;
+  unsigned* tab = (unsigned*)(ic_lds + IC_TC * IC_LDA);
+  unsigned* xs = tab + infer_conv_tab_words(K, RN);
+  const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
+  const unsigned nn = nw * nw;
+  const unsigned b = blockIdx.x / strips, p0 = (blockIdx.x % strips) * IC_TP, ch0 = blockIdx.y * IC_TC;
+  const unsigned pl = wave * 32 + l31, p = p0 + pl;
+  const bool tile_live = ch0 < u0 && p0 / nw < u1;                                         // (uniform in the workgroup)
+  const bool wave_live = tile_live && p0 + wave * 32 < nn && (p0 + wave * 32) / nw < u1;  // (uniform in the wave)
+  infer_v16i acc;
+#pragma unroll
+  for (int r = 0; r < 16; r++) acc[r] = 0;
+  if (tile_live) infer_conv_tile<RN>(acc, x, f, As, tab, xs, b, p0, ch0, tid, half, l31, pl, wave_live, kw, kx, ra, K, nw);
+  __syncthreads();  // (every wave has read its last fragments: the filter-slice buffer becomes the result tile)
+  const bool keep = wave_live && p < nn && p / nw < u1 && p % nw < u2;
+  const uint64_t lim = uint64_t(1) << bits;
+  unsigned bad = 0;
+#pragma unroll
+  for (int r = 0; r < 16; r++) {
+    const unsigned tc = (r & 3) + 8 * (r >> 2) + 4 * half, ch = ch0 + tc;
+    const int64_t v = keep && ch < u0 ? (int64_t)((uint64_t)(int64_t)acc[r] + (uint64_t)bias[ch]) : (int64_t)0;
+    const uint64_t mag = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
+    if (mag > lim && ch < kw && p < nn) bad |= 1u << r;
+    int64_t y = (int64_t)((uint64_t)v * (uint64_t)mult + (uint64_t(1) << (sh - 1))) >> sh;
+    y = y < -127 ? -127 : y > 127 ? 127 : y;
+    if (RELU) y = y < 0 ? 0 : y;
+    As[tc * IC_LDA + pl] = (int8_t)y;
+  }
+  if (__ballot(bad != 0)) { if (bad) infer_refuse(status, b, INFER_BAD_REQUANT); }
+  __syncthreads();
+  const unsigned live = nn - p0 < IC_TP ? nn - p0 : IC_TP;  // the pixels of the strip within the plane (a multiple of 16)
+  if (!POOL) {
+    const unsigned tc = tid >> 3, at = (tid & 7) * 16, ch = ch0 + tc;
+    if (ch < kw && at < live) *(infer_v4i*)(O8 + ((size_t)b * kw + ch) * nn + p0 + at) = *(const infer_v4i*)&As[tc * IC_LDA + at];
+    if (W64) {
+      for (unsigned i = tid; i < IC_TC * IC_TP / 2; i += 256) {
+        const unsigned c = i >> 6, e = (i & 63) * 2;
+        const int8_t* y = &As[c * IC_LDA + e];
+        if (ch0 + c < kw && e < live) { infer_v2l v; v[0] = y[0]; v[1] = y[1]; *(infer_v2l*)(O64 + ((size_t)b * kw + ch0 + c) * nn + p0 + e) = v; }
+      }
+    }
+  } else {
+    const unsigned np = live / 4, pn = nn / 4, pp0 = p0 / 4;  // pooled pixels: of the strip, of a plane, in front of the strip
+    if ((np & 15) == 0) {
+      const unsigned c = tid / (np / 16), j = tid % (np / 16) * 16;
+      if (c < IC_TC && ch0 + c < kw) {
+        infer_v4i v;
+#pragma unroll
+        for (int t = 0; t < 4; t++) v[t] = (int)infer_pool4(&As[c * IC_LDA], j + 4 * t, nw);
+        *(infer_v4i*)(O8 + ((size_t)b * kw + ch0 + c) * pn + pp0 + j) = v;
+      }
+    } else {
+      for (unsigned i = tid; i < IC_TC * np; i += 256) {
+        const unsigned c = i / np, j = i % np;
+        if (ch0 + c < kw) O8[((size_t)b * kw + ch0 + c) * pn + pp0 + j] = (int8_t)infer_pool1(&As[c * IC_LDA], j, nw);
+      }
+    }
+    if (W64) {
+      for (unsigned i = tid; i < IC_TC * np / 2; i += 256) {
+        const unsigned c = i / (np / 2), j = i % (np / 2) * 2;
+        if (ch0 + c < kw) { infer_v2l v; v[0] = infer_pool1(&As[c * IC_LDA], j, nw); v[1] = infer_pool1(&As[c * IC_LDA], j + 1, nw); *(infer_v2l*)(O64 + ((size_t)b * kw + ch0 + c) * pn + pp0 + j) = v; }
+      }
+    }
   }
 }
 // Activation::Gelu (gelu_op): table[v * mult + max], the table's rows being -max .. max - 1. |v| > 2^20 or a scaled value outside the table
@@ -773,9 +892,11 @@ static dim3 infer_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 // one op for the nb samples of the chunk: one launch. launches (INFER_COUNTS words): by kind the ops served, [IO_KINDS + 2]: the launches of
 // k_infer_gemm_i8 and k_infer_gemm_i8_rq, [IO_KINDS + 3]: those of k_infer_conv_i8, [IO_KINDS + 4]: those of k_infer_gemm2_i8 (all counted
 // under their kind as well), [IO_KINDS + 5]: those of k_infer_gemm_i8_rq, [IO_KINDS + 6]: the ops it absorbed — served, and counted under
-// their kinds, without a launch of their own. fuse: the head of a chain (infer_fuse_plan) whose input has its int8 form in this call takes
-// k_infer_gemm_i8_rq; the result is the number of ops absorbed (o.d[1], o.d[2]: the caller skips them), 0 for every other launch.
-constexpr size_t INFER_COUNTS = IO_KINDS + 7;
+// their kinds, without a launch of their own —, [IO_KINDS + 7]: the launches of k_infer_conv_i8_rq (counted under [IO_KINDS + 3] as well; the ops
+// it absorbed under [IO_KINDS + 6]). fuse: the head of a chain (infer_fuse_plan) whose input has its int8 form in this call takes
+// k_infer_gemm_i8_rq / k_infer_conv_i8_rq; the result is the number of ops absorbed (IO_GEMM: o.d[1], o.d[2], IO_CONV: o.fused — the caller skips
+// them), 0 for every other launch.
+constexpr size_t INFER_COUNTS = IO_KINDS + 8;
 static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferScratch& m, InferDeviceState* st, hipStream_t s, size_t nb, size_t* launches, bool fuse) {
   static const bool no_mfma = getenv("DP_INFER_NO_MFMA") && atoi(getenv("DP_INFER_NO_MFMA"));
   const bool i8 = infer_reads_int8_only(p, o, o.in0, m.q, nb, no_mfma);  // (the one predicate: also what infer_needs_int64 elides by)
@@ -835,9 +956,32 @@ static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferS
         DP_REQUIRE(nb * strips <= 0x7fffffffu, DP_ERR_ARG, "dp_model_infer: conv grid");
         const int8_t* f8 = infer_const8(p, st, o.w);
         const unsigned u0 = (unsigned)o.d[4], u1 = (unsigned)o.d[5], u2 = (unsigned)o.d[6];
+        launches[IO_KINDS + 3]++;
+        if (fuse && o.nfused) {  // the chain in one launch: o.fused = its Requant, then a ReLU and / or a MaxPool
+          const InferOp& rq = p.ops[(size_t)o.fused[0]];
+          const InferOp& lo = p.ops[(size_t)o.fused[o.nfused - 1]];
+          const bool relu = o.nfused >= 2 && p.ops[(size_t)o.fused[1]].kind == IO_RELU, pool = lo.kind == IO_MAXPOOL;
+          int64_t* o64 = infer_needs_int64(p, lo.out, m.q, nb, no_mfma) ? m.T64(lo.out) : nullptr;
+          auto go = [&](auto kern) { kern<<<grid, 256, lds, s>>>(m.T8(o.in0), f8, c64(o.bias), m.T8(lo.out), o64, strips, kw, kx, ra, K, nw, u0, u1, u2, rq.left, rq.shift, rq.bits, m.status()); };
+          auto pick = [&](auto r) {
+            constexpr int RN = decltype(r)::value;
+            switch ((relu ? 1 : 0) | (pool ? 2 : 0) | (o64 ? 4 : 0)) {
+              case 0: go(k_infer_conv_i8_rq<RN, false, false, false>); break;
+              case 1: go(k_infer_conv_i8_rq<RN, true, false, false>); break;
+              case 2: go(k_infer_conv_i8_rq<RN, false, true, false>); break;
+              case 3: go(k_infer_conv_i8_rq<RN, true, true, false>); break;
+              case 4: go(k_infer_conv_i8_rq<RN, false, false, true>); break;
+              case 5: go(k_infer_conv_i8_rq<RN, true, false, true>); break;
+              case 6: go(k_infer_conv_i8_rq<RN, false, true, true>); break;
+              default: go(k_infer_conv_i8_rq<RN, true, true, true>); break;
+            }
+          };
+          if (rn == 4) pick(std::integral_constant<int, 4>()); else pick(std::integral_constant<int, 8>());
+          launches[IO_REQUANT]++; launches[IO_RELU] += relu; launches[IO_MAXPOOL] += pool; launches[IO_KINDS + 7]++; launches[IO_KINDS + 6] += (size_t)o.nfused;
+          return (size_t)o.nfused;
+        }
         if (rn == 4) k_infer_conv_i8<4><<<grid, 256, lds, s>>>(m.T8(o.in0), f8, c64(o.bias), m.T64(o.out), strips, kw, kx, ra, K, nw, u0, u1, u2);
         else k_infer_conv_i8<8><<<grid, 256, lds, s>>>(m.T8(o.in0), f8, c64(o.bias), m.T64(o.out), strips, kw, kx, ra, K, nw, u0, u1, u2);
-        launches[IO_KINDS + 3]++;
       } else k_infer_conv<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), c64(o.bias), m.T64(o.out), n, o.d[0], o.d[1], o.d[2], o.d[3], o.d[4], o.d[5], o.d[6]);
       break;
     case IO_GELU: k_infer_gelu<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.table), m.T64(o.out), m.T8(o.out), m.TP(o.out, 0), m.TP(o.out, 1), n, o.left, (int64_t)o.d[0], m.status(), len); break;
@@ -881,14 +1025,14 @@ static uint32_t infer_enqueue(const InferProgram& p, const InferScratch& m, Infe
   }
   for (size_t i = 0; i < p.ops.size(); i++) {
     const InferOp& o = p.ops[i];
-    if (absorbed[i]) continue;  // (a Requant / ReLU the fused launch of its chain's head has served)
+    if (absorbed[i]) continue;  // (a Requant / ReLU / MaxPool the fused launch of its chain's head has served)
     if (o.kind == IO_SOFTMAX) {
       const auto ts = std::chrono::steady_clock::now();
       infer_shift_trip(p, o, m, s, nb);
       trips++; trip_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
       if (!checked) if (const uint32_t cls = infer_first_class(m.sm_status(), nb)) return cls;
     }
-    for (size_t k = infer_launch(p, o, m, st, s, nb, launches, fuse); k >= 1; k--) absorbed[o.d[k]] = 1;
+    for (size_t k = infer_launch(p, o, m, st, s, nb, launches, fuse); k >= 1; k--) absorbed[o.kind == IO_CONV ? (size_t)o.fused[k - 1] : o.d[k]] = 1;
   }
   return INFER_OK;
 }
@@ -971,8 +1115,8 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (wall_ms) *wall_ms = ms;
   const size_t n_i8 = launches[IO_KINDS + 2] + launches[IO_KINDS + 4], n_i64 = launches[IO_GEMM] + launches[IO_GEMM2] - n_i8;
-  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu gemm2_i8 %zu conv %zu conv_i8 %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu argmax %zu fused %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s%s\n",
-                   n_i8, n_i64, launches[IO_KINDS + 4], launches[IO_CONV], launches[IO_KINDS + 3], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], launches[IO_ARGMAX], launches[IO_KINDS + 5], trips, trip_ms,
+  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu gemm2_i8 %zu conv %zu conv_i8 %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu argmax %zu fused %zu conv_rq %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s%s\n",
+                   n_i8, n_i64, launches[IO_KINDS + 4], launches[IO_CONV], launches[IO_KINDS + 3], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], launches[IO_ARGMAX], launches[IO_KINDS + 5], launches[IO_KINDS + 7], trips, trip_ms,
                    ninputs, nchunks, chunk, (double)m.total / 1048576.0, m.in_q ? "int8" : "int64", ms,
                    taps ? ("; taps " + std::to_string(p.taps.size()) + " entries, " + std::to_string(p.row_words) + " words, pack_launches " + std::to_string(tap_launches) + " pack_ms " + std::to_string(tap_ms)).c_str() : "",
                    reasons ? ("; checked, refused " + std::to_string(nrefused)).c_str() : "");
