@@ -5,7 +5,8 @@
 // a Requant (through ReLU / MaxPool / Flatten), a model input the host has range-checked at upload, or a tensor whose values are bounded
 // whatever the data is (infer_range_plan below: the entries of a GELU or Embeddings table and sums of such): within -128..127 it gets an int8
 // copy, within -16384..16383 two int8 planes, the left operand of k_infer_gemm_i8_pl. A convolution is such a product too
-// (k_infer_conv_i8, on the packed filter image of infer_conv_pack) when its padded kernel side is 4 or 8. Everything else is 64-bit
+// (k_infer_conv_i8, on the packed filter image of infer_conv_pack) at every padded kernel side the kernel has a form for: 1 (a pointwise layer,
+// staged as a GEMM in K slices whatever the number of channels), 2, 4, 8 and 16. Everything else is 64-bit
 // multiply-add with the host's wrap-around. The product of two tensors of the batch (IO_GEMM2: MatMul2, ConcatMatMul, the two products of an Mha node)
 // takes k_infer_gemm2_i8 when infer_gemm2_plan below finds a form for both operands and both have int8 copies; the left one may instead be a
 // two-plane tensor (IQ_PLANES: the probabilities a Softmax writes, when every entry of its table lies in 0..16383, or a tensor of infer_range_plan).
@@ -79,11 +80,16 @@ struct InferOp {
 // k_infer_conv_i8 (infer_kernels.inc): a workgroup computes IC_TC output channels of a strip of IC_TP consecutive pixels of one sample's plane; the
 // filter tile goes through LDS in K slices of IC_TK bytes (row pitch IC_LDA). Its dynamic LDS, in this order: the filter slice, one word per
 // filter row of the packed K (where the row's input bytes start), and per input channel the span of int8 inputs the strip can touch —
-// IC_TP + (ra - 1) * nw + rn - 1 bytes, + 4 so that every fragment can be cut from whole aligned words, rounded up to 16
+// IC_TP + (ra - 1) * nw + rn - 1 bytes, + 4 so that every fragment can be cut from whole aligned words, rounded up to 16.
+// A pointwise layer (rn == 1, infer_conv_tile<1>) has no table and no spans: behind the filter slice lies the input slice, IC_TP pixels x IC_TK
+// channels at row pitch IC_LDA — 23040 bytes whatever kx is. infer_conv_lds is the one rule: infer_conv_pack admits by it, infer_launch sizes by it
 constexpr unsigned IC_TC = 32, IC_TP = 128, IC_TK = 128, IC_LDA = IC_TK + 16, IC_LDS_MAX = 48 * 1024;
 DP_HD unsigned infer_conv_pitch(unsigned nw, unsigned ra, unsigned rn) { return (IC_TP + (ra - 1) * nw + rn + 3 + 15) & ~15u; }
-DP_HD unsigned infer_conv_tab_words(unsigned K, unsigned rn) { return (K / rn + 3) & ~3u; }
-DP_HD size_t infer_conv_lds(size_t kx, unsigned nw, unsigned ra, unsigned rn, unsigned K) { return (size_t)IC_TC * IC_LDA + 4 * (size_t)infer_conv_tab_words(K, rn) + kx * infer_conv_pitch(nw, ra, rn); }
+DP_HD unsigned infer_conv_tab_words(unsigned K, unsigned rn) { return rn == 1 ? 0u : (K / rn + 3) & ~3u; }
+DP_HD size_t infer_conv_lds(size_t kx, unsigned nw, unsigned ra, unsigned rn, unsigned K) {
+  if (rn == 1) return (size_t)(IC_TC + IC_TP) * IC_LDA;
+  return (size_t)IC_TC * IC_LDA + 4 * (size_t)infer_conv_tab_words(K, rn) + kx * infer_conv_pitch(nw, ra, rn);
+}
 // The static half of "does this IO_GEMM2 take k_infer_gemm2_i8" (the other half, at the launch: both tensors have their int8 form in this call).
 // Each operand needs a unit stride along m (IG2_*K: staged with loads along K) or along its other matrix axis, r for A / n for B (IG2_*T: read along
 // that axis and transposed on the way into LDS); one whose unit stride is the concat axis is not served. K * 128 * 128 < 2^31 keeps the 32-bit
@@ -333,13 +339,14 @@ inline void infer_softmax_shifts(const LayerSpec& sm, const int64_t* x, size_t n
 // kernel side) and mostly padding: ra = the smallest number of leading filter rows that holds every non-zero weight of every filter of the
 // layer (at least 1). The image is [kw][K]: k = (j * ra + a) * rn + c for input channel j, filter row a < ra and column c < rn — c keeps the
 // padded rn, so rn consecutive k are rn consecutive input bytes —, zero padded from kx * ra * rn up to K, a multiple of the 32 of an MFMA
-// step. No image (w8 empty, ra = K = 0) unless rn is 4 or 8, nw a multiple of 4 (whole words of a plane are staged), every weight within
-// -128..127, K * 128 * 128 < 2^31 (the 32-bit accumulator is exact) and the kernel's LDS fits: the op then stays on k_infer_conv.
+// step; at rn = 1 (ra = 1) simply k = j. No image (w8 empty, ra = K = 0) unless rn is 1, 2, 4, 8 or 16, nw a multiple of 4 (whole words of a plane are staged), every weight within
+// -128..127, K * 128 * 128 < 2^31 (the 32-bit accumulator is exact) and the kernel's LDS fits (infer_conv_lds: the kx spans of rn >= 2 within
+// IC_LDS_MAX, so a wide 16-sided layer may not; a pointwise layer always does): the op then stays on k_infer_conv.
 struct InferConvImage { size_t ra = 0, K = 0; std::vector<int8_t> w8; };
 inline InferConvImage infer_conv_pack(const LayerSpec& l) {
   InferConvImage im;
   const size_t rn = l.real_nw, per = rn * rn, nf = l.kw * l.kx;
-  if ((rn != 4 && rn != 8) || l.nw % 4 || l.nw > 4096 || l.weights.size() != nf * per) return im;
+  if ((rn != 1 && rn != 2 && rn != 4 && rn != 8 && rn != 16) || l.nw % 4 || l.nw > 4096 || l.weights.size() != nf * per) return im;
   size_t ra = 1;
   for (size_t i = 0; i < nf * per; i++) {
     if (l.weights[i] < -128 || l.weights[i] > 127) return im;

@@ -484,9 +484,26 @@ __global__ __launch_bounds__(256) void k_infer_conv(const int64_t* __restrict__ 
 }
 // The pixel-side fragment of k_infer_conv_i8: the lane's 16 consecutive k are 16 / RN filter rows of RN columns, and the RN inputs under row
 // q are RN consecutive bytes of the staged span, from byte 4 * (tab[q] + wl) + sh on (wl, sh: the lane's pixel of the strip, as a word and the
-// byte within it). They are cut from whole aligned LDS words with v_alignbyte_b32, whatever sh is
+// byte within it). They are cut from whole aligned LDS words with v_alignbyte_b32, whatever sh is. RN == 2: eight rows of two bytes, two rows
+// packed per register with v_perm_b32; RN == 16: one row, five words, four cuts
 template <int RN> __device__ __forceinline__ infer_v4i infer_conv_frag(const unsigned* xs, const unsigned* tab, unsigned q, unsigned wl, unsigned sh) {
   infer_v4i v;
+  if (RN == 2) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const unsigned* w0 = xs + tab[q + 2 * r] + wl;
+      const unsigned* w1 = xs + tab[q + 2 * r + 1] + wl;
+      v[r] = (int)__builtin_amdgcn_perm(__builtin_amdgcn_alignbyte(w1[1], w1[0], sh), __builtin_amdgcn_alignbyte(w0[1], w0[0], sh), 0x05040100u);
+    }
+    return v;
+  }
+  if (RN == 16) {
+    const unsigned* w = xs + tab[q] + wl;
+    unsigned lo = w[0];
+#pragma unroll
+    for (int i = 0; i < 4; i++) { const unsigned hi = w[i + 1]; v[i] = (int)__builtin_amdgcn_alignbyte(hi, lo, sh); lo = hi; }
+    return v;
+  }
 #pragma unroll
   for (int r = 0; r < 16 / RN; r++) {
     const unsigned* w = xs + tab[q + r] + wl;
@@ -526,9 +543,75 @@ template <int RN> __device__ __forceinline__ void infer_conv_tile(infer_v16i& ac
     }
   }
 }
+// infer_conv_tile for a pointwise layer (RN == 1: k = j, K = kx rounded up to 32): out[b][ch][p] = sum over j of f[ch][j] * x[b][j][p] is a GEMM whose
+// tensor operand is contiguous along the PIXELS, so there are no spans and no row table (infer_conv_tab_words(K, 1) == 0): BOTH operands go through
+// LDS in K slices of IC_TK = 128 input channels, the filter tile into As as before, the inputs into Xs = [IC_TP pixels][IC_TK k] at row pitch
+// IC_LDA = 144 bytes, right behind As: IC_TC * IC_LDA + IC_TP * IC_LDA = 23040 bytes whatever kx is (infer_conv_lds).
+// Staging the inputs: a slice is 32 pixel quads x 32 channel quads of 4 x 4 bytes, four per thread. A wave takes 16 consecutive pixel quads (lanes
+// 0..15: 64 consecutive bytes of one channel's plane per load) x 4 consecutive channel quads; a thread loads the aligned word of its 4 pixels from
+// each of 4 consecutive channels, transposes the 4 x 4 bytes in registers (v_perm_b32, 8 per quad) and writes four words of 4 channels x 1 pixel
+// to Xs[pixel][4 cq ...]. Channels >= kx (the K padding and the rest of the last slice) and pixels >= nn are zeros in registers and are not read
+// from memory, filter rows >= kw and columns >= K likewise: nn is a multiple of 4 (infer_conv_pack), so a word at pixel 4 pq < nn of channel
+// j < kx of sample b < batch lies within x, and a 16-byte read of f at row < kw, column < K (a multiple of 32) within the image.
+// Banks: a row of 36 words. The fragment of a lane is ONE 16-byte read at word 36 * pixel + 8 s + 4 half; over 16 consecutive pixels 36 p mod 64
+// = 4 * (9 p mod 16) takes 16 different values: each quarter wave covers the 64 banks once. The transposed store of pixel 4 pq + i, channel quad
+// cq is word 36 * (4 pq + i) + cq = 16 pq + 36 i + cq (mod 64): with the same i in every lane the 16 pixel quads of a wave would share 4 banks.
+// So lane rotates its words by r = (pq >> 2) & 3 bytes (v_alignbyte_b32) before the transposition and its t-th store is pixel i = (t + r) & 3:
+// 16 (pq & 3) + 36 ((t + r) & 3) takes 16 values, all multiples of 4, and the 4 channel quads of the wave fill the words between them — the 64
+// lanes of a store hit 64 different banks. No prefetch into registers: the 16 words of the next slice would have to live across the MFMA steps;
+// the loads are issued in front of the barrier instead, while other waves still multiply the slice before.
+template <> __device__ __forceinline__ void infer_conv_tile<1>(infer_v16i& acc, const int8_t* __restrict__ x, const int8_t* __restrict__ f, int8_t* As, unsigned*, unsigned* xs, unsigned b, unsigned p0,
+                                                                unsigned ch0, unsigned tid, unsigned half, unsigned l31, unsigned pl, bool wave_live, unsigned kw, unsigned kx, unsigned, unsigned K,
+                                                                unsigned nw) {
+  int8_t* Xs = (int8_t*)xs;
+  const unsigned nn = nw * nw;
+  const unsigned lr = tid >> 3, lc = (tid & 7) * 16;                            // the 16 bytes of the filter slice this thread stages: tile row, byte column
+  const unsigned pq = (tid & 15) | ((tid >> 2) & 16), cq0 = ((tid >> 4) & 3) | ((tid >> 5) & 4);  // its pixel quad (0..31) and the first of its four channel quads (cq0 + 8 u)
+  const unsigned rot = (pq >> 2) & 3;
+  const bool px = p0 + 4 * pq < nn;
+  const int8_t* xp = x + (size_t)b * kx * nn + p0 + 4 * pq;
+  for (unsigned k0 = 0; k0 < K; k0 += IC_TK) {
+    infer_v4i a = {0, 0, 0, 0};
+    if (ch0 + lr < kw && k0 + lc < K) a = *(const infer_v4i*)(f + (size_t)(ch0 + lr) * K + k0 + lc);
+    unsigned w[4][4];  // w[u][i]: the 4 pixels of channel k0 + 4 * (cq0 + 8 u) + i
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const unsigned j = k0 + 4 * (cq0 + 8 * u) + i;
+        w[u][i] = px && j < kx ? *(const unsigned*)(xp + (size_t)j * nn) : 0u;
+      }
+    }
+    __syncthreads();  // (the fragments of the slice before have been read)
+    *(infer_v4i*)&As[lr * IC_LDA + lc] = a;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      unsigned r[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) r[i] = __builtin_amdgcn_alignbyte(w[u][i], w[u][i], rot);  // byte t = pixel (t + rot) & 3
+      const unsigned lo01 = __builtin_amdgcn_perm(r[1], r[0], 0x05010400u), hi01 = __builtin_amdgcn_perm(r[1], r[0], 0x07030602u);
+      const unsigned lo23 = __builtin_amdgcn_perm(r[3], r[2], 0x05010400u), hi23 = __builtin_amdgcn_perm(r[3], r[2], 0x07030602u);
+      const unsigned t4[4] = {__builtin_amdgcn_perm(lo23, lo01, 0x05040100u), __builtin_amdgcn_perm(lo23, lo01, 0x07060302u), __builtin_amdgcn_perm(hi23, hi01, 0x05040100u),
+                              __builtin_amdgcn_perm(hi23, hi01, 0x07060302u)};  // t4[t]: channels i = 0..3 (byte i) of pixel (t + rot) & 3
+#pragma unroll
+      for (unsigned t = 0; t < 4; t++) *(unsigned*)&Xs[(4 * pq + ((t + rot) & 3)) * IC_LDA + 4 * (cq0 + 8 * u)] = t4[t];
+    }
+    __syncthreads();
+    if (wave_live) {
+#pragma unroll
+      for (unsigned s = 0; s < IC_TK / 32; s++) {
+        if (k0 + s * 32 < K) {
+          const infer_v4i fa = *(const infer_v4i*)&As[l31 * IC_LDA + s * 32 + half * 16];
+          const infer_v4i fb = *(const infer_v4i*)&Xs[pl * IC_LDA + s * 32 + half * 16];
+          acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa, fb, acc, 0, 0, 0);
+        }
+      }
+    }
+  }
+}
 // k_infer_conv on the i8 MFMA, exact: out[b][ch][p] = bias[ch] + sum over (j, a, c) of x[b][j][p + a * nw + c] * f[ch][j][a][c] on the flat plane
 // index p < nn = nw * nw, then clear_garbage. x: the int8 copy of the input, [batch][kx][nn]; f: the packed filter image [kw][K] of
-// infer_conv_pack, k = (j * ra + a) * RN + c (RN = the padded kernel side, 4 or 8; K a multiple of 32 with K * 128 * 128 < 2^31).
+// infer_conv_pack, k = (j * ra + a) * RN + c (RN = the padded kernel side, 2, 4, 8 or 16; RN = 1: infer_conv_tile<1> above; K a multiple of 32 with K * 128 * 128 < 2^31).
 // A workgroup (4 waves) owns IC_TC = 32 output channels (blockIdx.y) of one strip of IC_TP = 128 consecutive pixels of one sample's plane
 // (blockIdx.x = sample * strips + strip: a strip never crosses a sample), a wave 32 channels x 32 pixels: one accumulator of
 // v_mfma_i32_32x32x32_i8 with the channels as its first operand and the pixels as its second, so that the D column — the lane — is the pixel and
@@ -948,7 +1031,7 @@ static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferS
     case IO_EMBED: k_infer_embed<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), m.T64(o.out), m.T8(o.out), m.TP(o.out, 0), m.TP(o.out, 1), n, o.d[0], o.d[1], m.status(), len); break;
     case IO_MAXPOOL: k_infer_maxpool<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.out), m.T8(o.out), n, o.d[1], o.d[2]); break;
     case IO_CONV:
-      if (i8) {  // (the planner made the image: rn is 4 or 8 and the LDS fits)
+      if (i8) {  // (the planner made the image: rn is 1, 2, 4, 8 or 16 and the LDS fits)
         const unsigned kw = (unsigned)o.d[0], kx = (unsigned)o.d[1], rn = (unsigned)o.d[2], nw = (unsigned)o.d[3], ra = (unsigned)o.d[7], K = (unsigned)o.g.K;
         const unsigned strips = (nw * nw + IC_TP - 1) / IC_TP;
         const dim3 grid((unsigned)(nb * strips), (kw + IC_TC - 1) / IC_TC);
@@ -956,6 +1039,15 @@ static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferS
         DP_REQUIRE(nb * strips <= 0x7fffffffu, DP_ERR_ARG, "dp_model_infer: conv grid");
         const int8_t* f8 = infer_const8(p, st, o.w);
         const unsigned u0 = (unsigned)o.d[4], u1 = (unsigned)o.d[5], u2 = (unsigned)o.d[6];
+        auto by_side = [&](auto go) {  // the instantiation of the padded kernel side
+          switch (rn) {
+            case 1: go(std::integral_constant<int, 1>()); break;
+            case 2: go(std::integral_constant<int, 2>()); break;
+            case 4: go(std::integral_constant<int, 4>()); break;
+            case 8: go(std::integral_constant<int, 8>()); break;
+            default: go(std::integral_constant<int, 16>()); break;
+          }
+        };
         launches[IO_KINDS + 3]++;
         if (fuse && o.nfused) {  // the chain in one launch: o.fused = its Requant, then a ReLU and / or a MaxPool
           const InferOp& rq = p.ops[(size_t)o.fused[0]];
@@ -976,12 +1068,11 @@ static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferS
               default: go(k_infer_conv_i8_rq<RN, true, true, true>); break;
             }
           };
-          if (rn == 4) pick(std::integral_constant<int, 4>()); else pick(std::integral_constant<int, 8>());
+          by_side(pick);
           launches[IO_REQUANT]++; launches[IO_RELU] += relu; launches[IO_MAXPOOL] += pool; launches[IO_KINDS + 7]++; launches[IO_KINDS + 6] += (size_t)o.nfused;
           return (size_t)o.nfused;
         }
-        if (rn == 4) k_infer_conv_i8<4><<<grid, 256, lds, s>>>(m.T8(o.in0), f8, c64(o.bias), m.T64(o.out), strips, kw, kx, ra, K, nw, u0, u1, u2);
-        else k_infer_conv_i8<8><<<grid, 256, lds, s>>>(m.T8(o.in0), f8, c64(o.bias), m.T64(o.out), strips, kw, kx, ra, K, nw, u0, u1, u2);
+        by_side([&](auto r) { k_infer_conv_i8<decltype(r)::value><<<grid, 256, lds, s>>>(m.T8(o.in0), f8, c64(o.bias), m.T64(o.out), strips, kw, kx, ra, K, nw, u0, u1, u2); });
       } else k_infer_conv<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), c64(o.bias), m.T64(o.out), n, o.d[0], o.d[1], o.d[2], o.d[3], o.d[4], o.d[5], o.d[6]);
       break;
     case IO_GELU: k_infer_gelu<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.table), m.T64(o.out), m.T8(o.out), m.TP(o.out, 0), m.TP(o.out, 1), n, o.left, (int64_t)o.d[0], m.status(), len); break;
