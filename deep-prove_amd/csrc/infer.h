@@ -6,7 +6,8 @@
 // whatever the data is (infer_range_plan below: the entries of a GELU or Embeddings table and sums of such): within -128..127 it gets an int8
 // copy, within -16384..16383 two int8 planes, the left operand of k_infer_gemm_i8_pl. A convolution is such a product too
 // (k_infer_conv_i8, on the packed filter image of infer_conv_pack) at every padded kernel side the kernel has a form for: 1 (a pointwise layer,
-// staged as a GEMM in K slices whatever the number of channels), 2, 4, 8 and 16. Everything else is 64-bit
+// staged as a GEMM in K slices whatever the number of channels), 2, 4, 8 and 16 (whole input spans in LDS where they fit, channel slices where they
+// do not: infer_conv_slice). Everything else is 64-bit
 // multiply-add with the host's wrap-around. The product of two tensors of the batch (IO_GEMM2: MatMul2, ConcatMatMul, the two products of an Mha node)
 // takes k_infer_gemm2_i8 when infer_gemm2_plan below finds a form for both operands and both have int8 copies; the left one may instead be a
 // two-plane tensor (IQ_PLANES: the probabilities a Softmax writes, when every entry of its table lies in 0..16383, or a tensor of infer_range_plan).
@@ -76,18 +77,35 @@ struct InferOp {
   // IO_CONV: the ops behind it that the epilogue of k_infer_conv_i8_rq absorbs (infer_fuse_plan), as indices in InferProgram::ops in chain
   // order: its Requant, then a ReLU and / or a MaxPool; nfused = 0: none
   int nfused = 0, fused[3] = {-1, -1, -1};
+  // IO_CONV: the input channels of a slice (infer_conv_slice) where the int8 image is served by the channel-sliced kernels; 0: unsliced
+  unsigned jc = 0;
 };
 // k_infer_conv_i8 (infer_kernels.inc): a workgroup computes IC_TC output channels of a strip of IC_TP consecutive pixels of one sample's plane; the
 // filter tile goes through LDS in K slices of IC_TK bytes (row pitch IC_LDA). Its dynamic LDS, in this order: the filter slice, one word per
 // filter row of the packed K (where the row's input bytes start), and per input channel the span of int8 inputs the strip can touch —
 // IC_TP + (ra - 1) * nw + rn - 1 bytes, + 4 so that every fragment can be cut from whole aligned words, rounded up to 16.
 // A pointwise layer (rn == 1, infer_conv_tile<1>) has no table and no spans: behind the filter slice lies the input slice, IC_TP pixels x IC_TK
-// channels at row pitch IC_LDA — 23040 bytes whatever kx is. infer_conv_lds is the one rule: infer_conv_pack admits by it, infer_launch sizes by it
-constexpr unsigned IC_TC = 32, IC_TP = 128, IC_TK = 128, IC_LDA = IC_TK + 16, IC_LDS_MAX = 48 * 1024;
+// channels at row pitch IC_LDA — 23040 bytes whatever kx is.
+// The channel-sliced form (rn >= 2, infer_conv_tile_sl) serves the layers whose kx spans do not fit: the input channels go through LDS in slices
+// of jc channels — jc * ra * rn consecutive k of the image —, two span buffers of jc spans each (rounded up to whole rounds of 256 words, one per thread of the
+// workgroup) behind a row table of jc * ra words that holds for every slice. infer_conv_slice is the slice rule: jc = the largest power of two with jc * pitch <= IC_SL_MAX (a slice is at most 4096 words: 16
+// per thread), jc * ra * rn a multiple of IC_TK (no K slice of the filter straddles two span slices; K = kx * ra * rn then, without padding) and
+// kx a multiple of jc; 0 where there is none (a very wide plane: the pitch alone passes IC_SL_MAX, or so few spans fit that they hold no whole K
+// slice). jc <= 64 (a pitch is at least 144), so its LDS is at most 4608 + 4 * 64 * 16 + 2 * IC_SL_MAX = 41472 bytes whatever kx is.
+// infer_conv_lds is the one rule (jc = 0: the whole-span form): infer_conv_pack admits by it, infer_launch sizes by it
+constexpr unsigned IC_TC = 32, IC_TP = 128, IC_TK = 128, IC_LDA = IC_TK + 16, IC_LDS_MAX = 48 * 1024, IC_SL_MAX = 16 * 1024;
 DP_HD unsigned infer_conv_pitch(unsigned nw, unsigned ra, unsigned rn) { return (IC_TP + (ra - 1) * nw + rn + 3 + 15) & ~15u; }
 DP_HD unsigned infer_conv_tab_words(unsigned K, unsigned rn) { return rn == 1 ? 0u : (K / rn + 3) & ~3u; }
-DP_HD size_t infer_conv_lds(size_t kx, unsigned nw, unsigned ra, unsigned rn, unsigned K) {
+DP_HD unsigned infer_conv_slice(unsigned kx, unsigned nw, unsigned ra, unsigned rn) {
+  if (rn < 2 || !kx) return 0;
+  const unsigned fit = IC_SL_MAX / infer_conv_pitch(nw, ra, rn);
+  unsigned jc = kx & (0u - kx);  // (the largest power of two that divides kx)
+  while (jc > fit) jc >>= 1;
+  return jc && jc * ra * rn % IC_TK == 0 ? jc : 0;  // (a smaller power of two has fewer factors of two still)
+}
+DP_HD size_t infer_conv_lds(size_t kx, unsigned nw, unsigned ra, unsigned rn, unsigned K, unsigned jc = 0) {
   if (rn == 1) return (size_t)(IC_TC + IC_TP) * IC_LDA;
+  if (jc) return (size_t)IC_TC * IC_LDA + 4 * (size_t)infer_conv_tab_words(jc * ra * rn, rn) + 2 * (((size_t)jc * infer_conv_pitch(nw, ra, rn) + 1023) & ~size_t(1023));
   return (size_t)IC_TC * IC_LDA + 4 * (size_t)infer_conv_tab_words(K, rn) + kx * infer_conv_pitch(nw, ra, rn);
 }
 // The static half of "does this IO_GEMM2 take k_infer_gemm2_i8" (the other half, at the launch: both tensors have their int8 form in this call).
@@ -340,9 +358,10 @@ inline void infer_softmax_shifts(const LayerSpec& sm, const int64_t* x, size_t n
 // layer (at least 1). The image is [kw][K]: k = (j * ra + a) * rn + c for input channel j, filter row a < ra and column c < rn — c keeps the
 // padded rn, so rn consecutive k are rn consecutive input bytes —, zero padded from kx * ra * rn up to K, a multiple of the 32 of an MFMA
 // step; at rn = 1 (ra = 1) simply k = j. No image (w8 empty, ra = K = 0) unless rn is 1, 2, 4, 8 or 16, nw a multiple of 4 (whole words of a plane are staged), every weight within
-// -128..127, K * 128 * 128 < 2^31 (the 32-bit accumulator is exact) and the kernel's LDS fits (infer_conv_lds: the kx spans of rn >= 2 within
-// IC_LDS_MAX, so a wide 16-sided layer may not; a pointwise layer always does): the op then stays on k_infer_conv.
-struct InferConvImage { size_t ra = 0, K = 0; std::vector<int8_t> w8; };
+// -128..127, K * 128 * 128 < 2^31 (the 32-bit accumulator is exact) and the kernel's LDS fits (infer_conv_lds): a pointwise layer always does; where
+// the kx spans of rn >= 2 fit IC_LDS_MAX the layer takes the whole-span form (jc = 0), otherwise the channel-sliced one where infer_conv_slice
+// has a jc for it; otherwise (a very wide plane) the op stays on k_infer_conv.
+struct InferConvImage { size_t ra = 0, K = 0; unsigned jc = 0; std::vector<int8_t> w8; };
 inline InferConvImage infer_conv_pack(const LayerSpec& l) {
   InferConvImage im;
   const size_t rn = l.real_nw, per = rn * rn, nf = l.kw * l.kx;
@@ -353,8 +372,13 @@ inline InferConvImage infer_conv_pack(const LayerSpec& l) {
     if (l.weights[i]) ra = std::max(ra, i % per / rn + 1);
   }
   const size_t K = (l.kx * ra * rn + 31) & ~size_t(31);
-  if (!((double)K * 128.0 * 128.0 < 2147483648.0) || infer_conv_lds(l.kx, (unsigned)l.nw, (unsigned)ra, (unsigned)rn, (unsigned)K) > IC_LDS_MAX) return im;
-  im.ra = ra; im.K = K; im.w8.assign(l.kw * K, 0);
+  if (!((double)K * 128.0 * 128.0 < 2147483648.0)) return im;
+  unsigned jc = 0;
+  if (infer_conv_lds(l.kx, (unsigned)l.nw, (unsigned)ra, (unsigned)rn, (unsigned)K) > IC_LDS_MAX) {
+    jc = infer_conv_slice((unsigned)l.kx, (unsigned)l.nw, (unsigned)ra, (unsigned)rn);
+    if (!jc || infer_conv_lds(l.kx, (unsigned)l.nw, (unsigned)ra, (unsigned)rn, (unsigned)K, jc) > IC_LDS_MAX) return im;
+  }
+  im.ra = ra; im.K = K; im.jc = jc; im.w8.assign(l.kw * K, 0);
   for (size_t f = 0; f < nf; f++) for (size_t a = 0; a < ra; a++) for (size_t c = 0; c < rn; c++)
     im.w8[f / l.kx * K + (f % l.kx * ra + a) * rn + c] = (int8_t)l.weights[(f * rn + a) * rn + c];
   return im;
@@ -504,7 +528,7 @@ inline InferProgram infer_plan(const ModelSpec& m, uint32_t flags = 0) {
       o.kind = IO_CONV; o.w = new_const(l.weights.data(), l.weights.size()); o.bias = new_const(l.bias.data(), l.bias.size());
       o.d[0] = l.kw; o.d[1] = l.kx; o.d[2] = l.real_nw; o.d[3] = l.nw; o.d[4] = l.unp_out[0]; o.d[5] = l.unp_out[1]; o.d[6] = l.unp_out[2];
       InferConvImage im = infer_conv_pack(l);
-      o.d[7] = im.ra; o.g.K = im.K; p.consts[(size_t)o.w].w8 = std::move(im.w8);
+      o.d[7] = im.ra; o.g.K = im.K; o.jc = im.jc; p.consts[(size_t)o.w].w8 = std::move(im.w8);
       o.out = new_tensor(l.kw * l.nw * l.nw, IQ_NO);
     } else if (l.kind == L_GELU) {
       const TableType tt = gelu_table(l);

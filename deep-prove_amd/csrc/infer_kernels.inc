@@ -609,6 +609,80 @@ template <> __device__ __forceinline__ void infer_conv_tile<1>(infer_v16i& acc, 
     }
   }
 }
+// infer_conv_tile in channel slices (RN >= 2), for the layers whose kx spans do not fit the LDS (infer_conv_pack): the same products in the same
+// order of k, but the input channels go through LDS jc = infer_conv_slice(kx, nw, ra, RN) at a time — jc * ra * RN consecutive k of the image, a
+// whole number of filter K slices, and K = kx * ra * RN has no padding. LDS behind As: the row table of ONE slice, jc * ra words (tab[q] = q / ra *
+// pw + q % ra * (nw / 4) does not depend on the slice: written once), then two span buffers of jc * pw words each, rounded up to whole rounds of 256
+// words (infer_conv_lds with jc).
+// Staging: a slice is jc * pw <= 4096 words = nt <= 16 rounds of the workgroup, and a thread owns words tid + 256 t, t < nt, of every slice:
+// where[t] = the word's byte offset from the slice's first span in x, worked out once (no division in the loop; jc <= 64 and nn <= 2^24 keep it
+// below 2^31), and keep[t] = all ones. A word past the slice (the padding of the last round, which no fragment reads) or at a pixel >= nn (which
+// must be zero) has keep[t] = 0 and reads the strip's first word in the slice's first channel instead: every lane loads, ANDs and stores in every
+// round, so no lane mask lives across the slice loop (sixteen of them would not fit the scalar registers; keep is opaque to the compiler for that
+// reason), and t < nt is a scalar test. The loads of slice s + 1 are issued in front of the MFMA steps of slice s into 16 registers, which live
+// across the steps, and are stored into the other buffer behind them. The hand-over has no barrier of its own: a wave stores slice s + 1 after the barriers
+// of the LAST filter slice of slice s, which every wave passes only behind its last fragment of slice s - 1 — the buffer's readers are done —, and
+// the two barriers of the first filter slice of slice s + 1 lie between these stores and the first fragment cut from them. Within a slice the
+// filter tile goes through As in K slices of IC_TK exactly as in infer_conv_tile; the fragment rule is infer_conv_frag on the slice's own q.
+// In bounds: word t of a slice is channel s * jc + i / pw < kx (i < jc * pw, s < kx / jc, kx a multiple of jc) at pixel p0 + 4 * (i % pw) < nn
+// (checked; words at or beyond nn are zeros in registers and are not read: their lanes read offset 0, pixel p0 < nn of channel s * jc): a whole
+// aligned word of x, as nn is a multiple of 4. A store of round t < nt lands at word tid + 256 t < 256 nt of the slice's own buffer. The 16-byte reads
+// of f lie at row < kw and column s * ks + k0 + lc + 15 < K. LDS: table and buffers as sized by infer_conv_lds; a fragment reads tab[q .. q + 16 /
+// RN) with q + 16 / RN <= jc * ra (ks is a multiple of 128) and span words within one pitch of its row's span, as in the whole-span form.
+template <int RN> __device__ __forceinline__ void infer_conv_tile_sl(infer_v16i& acc, const int8_t* __restrict__ x, const int8_t* __restrict__ f, int8_t* As, unsigned* tab, unsigned b, unsigned p0,
+                                                                     unsigned ch0, unsigned tid, unsigned half, unsigned l31, unsigned pl, bool wave_live, unsigned kw, unsigned kx, unsigned ra, unsigned K,
+                                                                     unsigned nw) {
+  const unsigned nn = nw * nw, pw = infer_conv_pitch(nw, ra, RN) / 4;  // (the pitch of a span in words)
+  const unsigned jc = infer_conv_slice(kx, nw, ra, RN), sw = jc * pw, ks = jc * ra * RN;  // per slice: channels, span words, k
+  unsigned* xs = tab + infer_conv_tab_words(ks, RN);
+  for (unsigned q = tid; q < jc * ra; q += 256) tab[q] = q / ra * pw + q % ra * (nw / 4);
+  const unsigned nt = (sw + 255) / 256, bw = 256 * nt;  // the rounds of a slice, the words of a span buffer
+  unsigned where[16], keep[16], w[16];
+#pragma unroll
+  for (unsigned t = 0; t < 16; t++) {
+    const unsigned i = tid + 256 * t, at = 4 * (i % pw);
+    const bool in = i < sw && p0 + at < nn;
+    where[t] = in ? i / pw * nn + at : 0u;
+    keep[t] = in ? 0xffffffffu : 0u;
+    asm volatile("" : "+v"(keep[t]));
+  }
+  const int8_t* xp = x + (size_t)b * kx * nn + p0;  // the strip's first pixel in channel 0; a slice further on: + jc * nn
+#pragma unroll
+  for (unsigned t = 0; t < 16; t++) if (t < nt) w[t] = *(const unsigned*)(xp + where[t]) & keep[t];
+#pragma unroll
+  for (unsigned t = 0; t < 16; t++) if (t < nt) xs[tid + 256 * t] = w[t];
+  const unsigned lr = tid >> 3, lc = (tid & 7) * 16;  // the 16 bytes of the filter slice this thread stages: tile row, byte column
+  const int8_t* fp = f + (size_t)(ch0 + lr) * K + lc;
+  for (unsigned s = 0, kb = 0; kb < K; s++, kb += ks) {
+    const unsigned* cur = xs + (s & 1) * bw;
+    const bool more = kb + ks < K;
+    if (more) {
+      xp += (size_t)jc * nn;
+#pragma unroll
+      for (unsigned t = 0; t < 16; t++) if (t < nt) w[t] = *(const unsigned*)(xp + where[t]) & keep[t];
+    }
+    for (unsigned k0 = 0; k0 < ks; k0 += IC_TK) {
+      infer_v4i a = {0, 0, 0, 0};
+      if (ch0 + lr < kw) a = *(const infer_v4i*)(fp + kb + k0);
+      __syncthreads();  // (the fragments of the slice before have been read)
+      *(infer_v4i*)&As[lr * IC_LDA + lc] = a;
+      __syncthreads();  // (the first one of a span slice: its spans are in LDS, too; the very first: the table)
+      if (wave_live) {
+#pragma unroll
+        for (unsigned u = 0; u < IC_TK / 32; u++) {
+          const infer_v4i fa = *(const infer_v4i*)&As[l31 * IC_LDA + u * 32 + half * 16];
+          const infer_v4i fb = infer_conv_frag<RN>(cur, tab, (k0 + u * 32 + half * 16) / RN, pl >> 2, pl & 3);
+          acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa, fb, acc, 0, 0, 0);
+        }
+      }
+    }
+    if (more) {
+      unsigned* nxt = xs + ((s + 1) & 1) * bw;
+#pragma unroll
+      for (unsigned t = 0; t < 16; t++) if (t < nt) nxt[tid + 256 * t] = w[t];
+    }
+  }
+}
 // k_infer_conv on the i8 MFMA, exact: out[b][ch][p] = bias[ch] + sum over (j, a, c) of x[b][j][p + a * nw + c] * f[ch][j][a][c] on the flat plane
 // index p < nn = nw * nw, then clear_garbage. x: the int8 copy of the input, [batch][kx][nn]; f: the packed filter image [kw][K] of
 // infer_conv_pack, k = (j * ra + a) * RN + c (RN = the padded kernel side, 2, 4, 8 or 16; RN = 1: infer_conv_tile<1> above; K a multiple of 32 with K * 128 * 128 < 2^31).
@@ -626,8 +700,9 @@ template <> __device__ __forceinline__ void infer_conv_tile<1>(infer_v16i& acc, 
 // Every term that leaves the plane or wraps into the next row belongs to an output clear_garbage zeroes, so a workgroup whose channels are all
 // >= u0 or whose rows are all >= u1 stages nothing and stores zeros, and so does such a wave of a live workgroup. In bounds: sample < batch
 // (the grid), word reads of x below nn, 16-byte reads of f below row kw and column K, LDS reads within a span (infer_conv_pitch), stores at
-// ch < kw and p < nn.
-template <int RN> __global__ __launch_bounds__(256) void k_infer_conv_i8(const int8_t* __restrict__ x, const int8_t* __restrict__ f, const int64_t* __restrict__ bias, int64_t* __restrict__ o,
+// ch < kw and p < nn. SL: the spans go through LDS in channel slices (infer_conv_tile_sl, for the layers whose kx spans do not fit); grid, fragments,
+// stores and the short cuts of dead tiles and waves are the same.
+template <int RN, bool SL = false> __global__ __launch_bounds__(256) void k_infer_conv_i8(const int8_t* __restrict__ x, const int8_t* __restrict__ f, const int64_t* __restrict__ bias, int64_t* __restrict__ o,
                                                                           unsigned strips, unsigned kw, unsigned kx, unsigned ra, unsigned K, unsigned nw, unsigned u0, unsigned u1, unsigned u2) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ic_lds[];
   int8_t* As = (int8_t*)ic_lds;
@@ -642,7 +717,10 @@ template <int RN> __global__ __launch_bounds__(256) void k_infer_conv_i8(const i
   infer_v16i acc;
 #pragma unroll
   for (int r = 0; r < 16; r++) acc[r] = 0;
-  if (tile_live) infer_conv_tile<RN>(acc, x, f, As, tab, xs, b, p0, ch0, tid, half, l31, pl, wave_live, kw, kx, ra, K, nw);
+  if (tile_live) {
+    if constexpr (SL) infer_conv_tile_sl<RN>(acc, x, f, As, tab, b, p0, ch0, tid, half, l31, pl, wave_live, kw, kx, ra, K, nw);
+    else infer_conv_tile<RN>(acc, x, f, As, tab, xs, b, p0, ch0, tid, half, l31, pl, wave_live, kw, kx, ra, K, nw);
+  }
   if (p >= nn) return;
   const bool keep = wave_live && p / nw < u1 && p % nw < u2;
   int64_t* op = o + (size_t)b * kw * nn + p;
@@ -695,7 +773,7 @@ __device__ __forceinline__ unsigned infer_pool4(const int8_t* row, unsigned j, u
 //     a channel row is 16-aligned: the int64 form starts 256-aligned and nn, nn / 4, p0 and p0 / 4 are even).
 // In bounds: as k_infer_conv_i8 for the loads; bias[ch] at ch < u0 <= kw; LDS within the tile (rows < 32, pixels < 128; a pooled pixel j <
 //   min(128, nn) / 4 reads rows 2 pr and 2 pr + 1 < min(128, nn) / nw); stores at ch < kw and p < nn (pooled: p0 / 4 + j < nn / 4).
-template <int RN, bool RELU, bool POOL, bool W64> __global__ __launch_bounds__(256) void k_infer_conv_i8_rq(const int8_t* __restrict__ x, const int8_t* __restrict__ f, const int64_t* __restrict__ bias,
+template <int RN, bool RELU, bool POOL, bool W64, bool SL = false> __global__ __launch_bounds__(256) void k_infer_conv_i8_rq(const int8_t* __restrict__ x, const int8_t* __restrict__ f, const int64_t* __restrict__ bias,
     int8_t* __restrict__ O8, int64_t* __restrict__ O64, unsigned strips, unsigned kw, unsigned kx, unsigned ra, unsigned K, unsigned nw, unsigned u0, unsigned u1, unsigned u2, int64_t mult, unsigned sh,
     unsigned bits, unsigned* status) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ic_lds[];
@@ -711,7 +789,10 @@ template <int RN, bool RELU, bool POOL, bool W64> __global__ __launch_bounds__(2
   infer_v16i acc;
 #pragma unroll
   for (int r = 0; r < 16; r++) acc[r] = 0;
-  if (tile_live) infer_conv_tile<RN>(acc, x, f, As, tab, xs, b, p0, ch0, tid, half, l31, pl, wave_live, kw, kx, ra, K, nw);
+  if (tile_live) {
+    if constexpr (SL) infer_conv_tile_sl<RN>(acc, x, f, As, tab, b, p0, ch0, tid, half, l31, pl, wave_live, kw, kx, ra, K, nw);
+    else infer_conv_tile<RN>(acc, x, f, As, tab, xs, b, p0, ch0, tid, half, l31, pl, wave_live, kw, kx, ra, K, nw);
+  }
   __syncthreads();  // (every wave has read its last fragments: the filter-slice buffer becomes the result tile)
   const bool keep = wave_live && p < nn && p / nw < u1 && p % nw < u2;
   const uint64_t lim = uint64_t(1) << bits;
@@ -1031,21 +1112,28 @@ static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferS
     case IO_EMBED: k_infer_embed<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), m.T64(o.out), m.T8(o.out), m.TP(o.out, 0), m.TP(o.out, 1), n, o.d[0], o.d[1], m.status(), len); break;
     case IO_MAXPOOL: k_infer_maxpool<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.out), m.T8(o.out), n, o.d[1], o.d[2]); break;
     case IO_CONV:
-      if (i8) {  // (the planner made the image: rn is 1, 2, 4, 8 or 16 and the LDS fits)
+      if (i8) {  // (the planner made the image: rn is 1, 2, 4, 8 or 16 and the LDS fits, whole spans or — o.jc — in channel slices)
         const unsigned kw = (unsigned)o.d[0], kx = (unsigned)o.d[1], rn = (unsigned)o.d[2], nw = (unsigned)o.d[3], ra = (unsigned)o.d[7], K = (unsigned)o.g.K;
         const unsigned strips = (nw * nw + IC_TP - 1) / IC_TP;
         const dim3 grid((unsigned)(nb * strips), (kw + IC_TC - 1) / IC_TC);
-        const size_t lds = infer_conv_lds(kx, nw, ra, rn, K);
+        const size_t lds = infer_conv_lds(kx, nw, ra, rn, K, o.jc);
+        DP_REQUIRE(o.jc == (o.jc ? infer_conv_slice(kx, nw, ra, rn) : 0u), DP_ERR_ARG, "dp_model_infer: conv slices");  // (the kernel works jc out by the same rule)
         DP_REQUIRE(nb * strips <= 0x7fffffffu, DP_ERR_ARG, "dp_model_infer: conv grid");
         const int8_t* f8 = infer_const8(p, st, o.w);
         const unsigned u0 = (unsigned)o.d[4], u1 = (unsigned)o.d[5], u2 = (unsigned)o.d[6];
-        auto by_side = [&](auto go) {  // the instantiation of the padded kernel side
-          switch (rn) {
-            case 1: go(std::integral_constant<int, 1>()); break;
-            case 2: go(std::integral_constant<int, 2>()); break;
-            case 4: go(std::integral_constant<int, 4>()); break;
-            case 8: go(std::integral_constant<int, 8>()); break;
-            default: go(std::integral_constant<int, 16>()); break;
+        auto by_side = [&](auto go) {  // the instantiation of the padded kernel side, whole spans or channel slices (rn >= 2 only)
+          if (o.jc) switch (rn) {
+            case 2: go(std::integral_constant<int, 2>(), std::true_type()); break;
+            case 4: go(std::integral_constant<int, 4>(), std::true_type()); break;
+            case 8: go(std::integral_constant<int, 8>(), std::true_type()); break;
+            default: go(std::integral_constant<int, 16>(), std::true_type()); break;
+          }
+          else switch (rn) {
+            case 1: go(std::integral_constant<int, 1>(), std::false_type()); break;
+            case 2: go(std::integral_constant<int, 2>(), std::false_type()); break;
+            case 4: go(std::integral_constant<int, 4>(), std::false_type()); break;
+            case 8: go(std::integral_constant<int, 8>(), std::false_type()); break;
+            default: go(std::integral_constant<int, 16>(), std::false_type()); break;
           }
         };
         launches[IO_KINDS + 3]++;
@@ -1055,24 +1143,25 @@ static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferS
           const bool relu = o.nfused >= 2 && p.ops[(size_t)o.fused[1]].kind == IO_RELU, pool = lo.kind == IO_MAXPOOL;
           int64_t* o64 = infer_needs_int64(p, lo.out, m.q, nb, no_mfma) ? m.T64(lo.out) : nullptr;
           auto go = [&](auto kern) { kern<<<grid, 256, lds, s>>>(m.T8(o.in0), f8, c64(o.bias), m.T8(lo.out), o64, strips, kw, kx, ra, K, nw, u0, u1, u2, rq.left, rq.shift, rq.bits, m.status()); };
-          auto pick = [&](auto r) {
+          auto pick = [&](auto r, auto sl) {
             constexpr int RN = decltype(r)::value;
+            constexpr bool SL = decltype(sl)::value;
             switch ((relu ? 1 : 0) | (pool ? 2 : 0) | (o64 ? 4 : 0)) {
-              case 0: go(k_infer_conv_i8_rq<RN, false, false, false>); break;
-              case 1: go(k_infer_conv_i8_rq<RN, true, false, false>); break;
-              case 2: go(k_infer_conv_i8_rq<RN, false, true, false>); break;
-              case 3: go(k_infer_conv_i8_rq<RN, true, true, false>); break;
-              case 4: go(k_infer_conv_i8_rq<RN, false, false, true>); break;
-              case 5: go(k_infer_conv_i8_rq<RN, true, false, true>); break;
-              case 6: go(k_infer_conv_i8_rq<RN, false, true, true>); break;
-              default: go(k_infer_conv_i8_rq<RN, true, true, true>); break;
+              case 0: go(k_infer_conv_i8_rq<RN, false, false, false, SL>); break;
+              case 1: go(k_infer_conv_i8_rq<RN, true, false, false, SL>); break;
+              case 2: go(k_infer_conv_i8_rq<RN, false, true, false, SL>); break;
+              case 3: go(k_infer_conv_i8_rq<RN, true, true, false, SL>); break;
+              case 4: go(k_infer_conv_i8_rq<RN, false, false, true, SL>); break;
+              case 5: go(k_infer_conv_i8_rq<RN, true, false, true, SL>); break;
+              case 6: go(k_infer_conv_i8_rq<RN, false, true, true, SL>); break;
+              default: go(k_infer_conv_i8_rq<RN, true, true, true, SL>); break;
             }
           };
           by_side(pick);
           launches[IO_REQUANT]++; launches[IO_RELU] += relu; launches[IO_MAXPOOL] += pool; launches[IO_KINDS + 7]++; launches[IO_KINDS + 6] += (size_t)o.nfused;
           return (size_t)o.nfused;
         }
-        by_side([&](auto r) { k_infer_conv_i8<decltype(r)::value><<<grid, 256, lds, s>>>(m.T8(o.in0), f8, c64(o.bias), m.T64(o.out), strips, kw, kx, ra, K, nw, u0, u1, u2); });
+        by_side([&](auto r, auto sl) { k_infer_conv_i8<decltype(r)::value, decltype(sl)::value><<<grid, 256, lds, s>>>(m.T8(o.in0), f8, c64(o.bias), m.T64(o.out), strips, kw, kx, ra, K, nw, u0, u1, u2); });
       } else k_infer_conv<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.w), c64(o.bias), m.T64(o.out), n, o.d[0], o.d[1], o.d[2], o.d[3], o.d[4], o.d[5], o.d[6]);
       break;
     case IO_GELU: k_infer_gelu<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), c64(o.table), m.T64(o.out), m.T8(o.out), m.TP(o.out, 0), m.TP(o.out, 1), n, o.left, (int64_t)o.d[0], m.status(), len); break;

@@ -43,7 +43,8 @@
  * operand is contiguous along the summed axis or along its other matrix axis, K * 128 * 128 < 2^31, the right operand is within -128..127 (a
  * Requant's output, or a model input of a call whose inputs all are) and the left one is too or is a Softmax's output; `conv N` counts
  * every convolution launch and `conv_i8 N`, directly after it, those of them that ran on the i8 MFMA — weights within -128..127 and a kernel
- * of 1 x 1 up to 16 x 16 (padded kernel side 1, 2, 4, 8 or 16; a 1 x 1 layer of any number of channels) —; gelu / layernorm / softmax launches,
+ * of 1 x 1 up to 16 x 16 (padded kernel side 1, 2, 4, 8 or 16; a 1 x 1 layer of any number of channels) —, many-channel layers whose input
+ * spans pass the LDS in slices of input channels (counted like the others; only on very wide planes no slice fits); gelu / layernorm / softmax launches,
  * shift_trips = round trips of the Softmax shift step and shift_ms = the milliseconds spent in them; a checked call appends
  * `; checked, refused N`), DP_PROVE_TRACE_MB (host memory for the trace rows of one segment of dp_model_prove_batch_ex, default 4096).
  */
