@@ -72,10 +72,12 @@ struct InferOp {
   // IO_EMBED: vocabulary, embedding size; IO_MAXPOOL: c, h, w; IO_CONV: kw, kx, real_nw, nw, unp_out[3], ra (the filter rows of the int8 image; 0: none, the op stays on k_infer_conv); IO_GELU: max; IO_LAYERNORM: row length, N;
   // IO_SOFTMAX: C, R, K, zero chunks, zero vars (in1 = the shift buffer of the chunk, a tensor of C * R words per sample); IO_ARGMAX: rows, K;
   // IO_GEMM2: d[0] = infer_gemm2_plan (IG2_*; 0: the op stays on k_infer_gemm_i64); IO_GEMM: d[0] = the ops behind it that k_infer_gemm_i8_rq
-  // absorbs (infer_fuse_plan: 0 none, 1 its Requant, 2 the Requant and a ReLU), d[1], d[2] = their indices in InferProgram::ops
+  // absorbs (infer_fuse_plan: 0 none, 1 its Requant, 2 the Requant and a ReLU), d[1], d[2] = their indices in InferProgram::ops.
+  // An IO_GEMM2 at the head of a chain of k_infer_gemm2_i8_rq (nfused = 1, fused[0] = its Requant): d[1] = IG2_OW | IG2_SM* (the wide store; with
+  // IG2_SM the Softmax in front of it is made on the way into LDS), d[2] = that Softmax's index in InferProgram::ops. The IO_SOFTMAX such a chain serves: d[5] = 1 + the index of the chain's IO_GEMM2 (0: none)
   size_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // IO_CONV: the ops behind it that the epilogue of k_infer_conv_i8_rq absorbs (infer_fuse_plan), as indices in InferProgram::ops in chain
-  // order: its Requant, then a ReLU and / or a MaxPool; nfused = 0: none
+  // order: its Requant, then a ReLU and / or a MaxPool; nfused = 0: none. IO_GEMM2: the Requant the epilogue of k_infer_gemm2_i8_rq absorbs
   int nfused = 0, fused[3] = {-1, -1, -1};
   // IO_CONV: the input channels of a slice (infer_conv_slice) where the int8 image is served by the channel-sliced kernels; 0: unsliced
   unsigned jc = 0;
@@ -126,6 +128,33 @@ inline unsigned infer_gemm2_plan(const InferGemmShape& g, size_t lenA, size_t le
   const int a = form(g.sAm, g.sAr, g.sAc, g.R, lenA, IG2_AT, IG2_AW), b = form(g.sBm, g.sBn, g.sBc, g.N, lenB, IG2_BT, IG2_BW);
   return a < 0 || b < 0 ? 0 : IG2_OK | (unsigned)a | (unsigned)b;
 }
+// k_infer_gemm2_i8_rq (InferOp::d[1] of the chain's IO_GEMM2; the kernel takes d[0] | d[1]). IG2_OW: the int8 tile leaves in 16-byte vectors along n
+// (sOn == 1 and N, the row and concat strides and the words of a sample are multiples of 16: the int8 copy of a tensor starts 256-aligned).
+// IG2_SM: the left operand is made from the Softmax's int64 input; IG2_SM_LDS: its exponential table is staged in LDS as 16-bit entries
+// (infer_gemm2_rq_table_lds; otherwise the 16-bit table is gathered through global memory); IG2_SM_SKIP: a masked element is 0, so the K slices
+// wholly above the diagonal of the tile's rows are skipped
+constexpr unsigned IG2_OW = 32, IG2_SM = 64, IG2_SM_LDS = 128, IG2_SM_SKIP = 256;
+// the LDS of k_infer_gemm2_i8_rq: three (SM: two planes of A, and B) or two operand slices of 64 rows at pitch 80, and behind them the table
+constexpr size_t IG2_RQ_LDS_MAX = 48 * 1024, IG2_RQ_OPERANDS = 3 * 64 * 80;
+// (tv <= 14. A diagnostic build with -DDP_IG2_TABLE_GATHER gathers every table through global memory: the measurement of the other form)
+#ifdef DP_IG2_TABLE_GATHER
+DP_HD bool infer_gemm2_rq_table_lds(unsigned) { return false; }
+#else
+DP_HD bool infer_gemm2_rq_table_lds(unsigned tv) { return tv >= 3 && IG2_RQ_OPERANDS + (size_t(2) << tv) <= IG2_RQ_LDS_MAX; }
+#endif
+// Softmax::evaluate on one element after the mask and the shift (called by k_infer_softmax, by k_infer_gemm2_i8_rq and by the planner: the arithmetic exists once): |masked| = low byte | high
+// byte | exponential table index (tv bits) | zero chunks (zc groups of zv bits). The index, and whether every zero chunk is zero: the value is
+// table[index] then, else 0. The index is masked: nothing is read outside the table, whatever the data
+DP_HD bool infer_softmax_index(int64_t masked, unsigned tv, unsigned zc, unsigned zv, size_t* index) {
+  int64_t r = masked < 0 ? (int64_t)(0 - (uint64_t)masked) : masked;
+  r >>= 16;
+  *index = (size_t)(r & ((int64_t(1) << tv) - 1));
+  r >>= tv;
+  bool keep = true;
+  for (unsigned z = 0; z < zc; z++) { keep = keep && (r & ((int64_t(1) << zv) - 1)) == 0; r >>= zv; }
+  return keep;
+}
+DP_HD int64_t infer_softmax_neg_inf(int64_t bkm) { return -(((bkm >> 16) + 1) << 16); }
 struct InferTap { int tensor = -1; size_t len = 0, off = 0; };  // words off .. off + len of a trace row are tensor `tensor`
 struct InferProgram {
   size_t input_len = 0, output_len = 0;
@@ -162,6 +191,13 @@ inline bool infer_needs_int64(const InferProgram& p, int t, const std::vector<ch
   for (const InferOp& o : p.ops) if ((o.in0 == t || o.in1 == t) && !infer_reads_int8_only(p, o, t, q, nb, no_mfma)) return true;
   return false;
 }
+// The form k_infer_gemm2_i8_rq takes for the chain at IO_GEMM2 o in this call: 0 none (today's launches), 1 SM = false, 2 SM = true. The same
+// per-call conditions as k_infer_gemm2_i8 (infer_reads_int8_only: the right operand has its int8 form, the tiles fit, no DP_INFER_NO_MFMA); the
+// launch of the product and the skipped launch of the Softmax (infer_launch) both ask here, so they cannot drift apart
+inline int infer_gemm2_rq_form(const InferProgram& p, const InferOp& o, const std::vector<char>& q, size_t nb, bool no_mfma) {
+  if (o.kind != IO_GEMM2 || !o.nfused || !infer_reads_int8_only(p, o, o.in0, q, nb, no_mfma)) return 0;
+  return (o.d[1] & IG2_SM) ? 2 : q[(size_t)o.in0] == IQ_YES ? 1 : 0;
+}
 // The chains k_infer_gemm_i8_rq serves in one launch, marked on the finished program (the last step of infer_plan): an IO_GEMM whose constant has
 // an int8 copy and whose output has exactly one reader, an IO_REQUANT with shift >= 1, and is no model output; and behind that, where the
 // Requant's output likewise has exactly one reader, an IO_RELU, and is no model output, the ReLU too. The absorbed ops run at the head's place
@@ -172,6 +208,17 @@ inline bool infer_needs_int64(const InferProgram& p, int t, const std::vector<ch
 // then optionally a ReLU, then optionally — behind the ReLU or straight behind the Requant — a MaxPool. The MaxPool is absorbed only where a
 // strip of IC_TP pixels holds whole pairs of rows (nw <= 64 and a divisor of IC_TP) and its (c, h, w) are the conv's (kw, nw, nw); otherwise the
 // chain ends in front of it and k_infer_maxpool runs.
+// The chains k_infer_gemm2_i8_rq serves, under the same rules: an IO_GEMM2 that infer_gemm2_plan has a form for and its Requant with shift >= 1
+// (fused[0]), where the left operand has an int8 copy (IQ_YES, or IQ_IF_INPUTS: per call) — SM = false —; or where the left operand is the
+// output of an IO_SOFTMAX of the two-plane kind (IQ_PLANES) that nothing else reads, that is no model output and that the product reads in the
+// Softmax's own layout (g.C, g.R, g.K = its C, R, K; sAm = 1, sAr = K, sAc = R K) — SM = true: the Softmax (d[2]; its d[5] points back) is made
+// on the way into LDS and neither the probabilities nor their planes are written. The Softmax's shift step stays where the Softmax is, and the
+// fused launch runs at the product's place. A product on planes in any other layout, or on planes with another reader, keeps its launches.
+// (The 16-bit image of the Softmax's table — every entry is within 0..16383 — becomes the w8 of the table's constant: little-endian pairs.)
+inline int64_t infer_softmax_masked(const InferProgram& p, const InferOp& sm) {
+  size_t idx = 0;
+  return infer_softmax_index(infer_softmax_neg_inf(sm.right), sm.bits, (unsigned)sm.d[3], (unsigned)sm.d[4], &idx) ? p.consts[(size_t)sm.table].data()[idx] : 0;
+}
 inline void infer_fuse_plan(InferProgram& p) {
   const size_t nt = p.tensors.size(), no = p.ops.size();
   std::vector<int> readers(nt, 0), reader(nt, -1);
@@ -195,6 +242,27 @@ inline void infer_fuse_plan(InferProgram& p) {
       const int mp = sole(p.ops[(size_t)(rl < 0 ? rq : rl)].out, IO_MAXPOOL, i);
       const size_t kw = o.d[0], nw = o.d[3];
       if (mp >= 0 && nw <= 64 && IC_TP % nw == 0 && p.ops[(size_t)mp].d[0] == kw && p.ops[(size_t)mp].d[1] == nw && p.ops[(size_t)mp].d[2] == nw) o.fused[o.nfused++] = mp;
+      continue;
+    }
+    if (o.kind == IO_GEMM2 && (o.d[0] & IG2_OK)) {
+      const int rq = sole(o.out, IO_REQUANT, i), qa = p.tensors[(size_t)o.in0].q;
+      if (rq < 0 || p.ops[(size_t)rq].shift < 1) continue;
+      const InferGemmShape& g = o.g;
+      const size_t lenO = p.tensors[(size_t)o.out].len;
+      size_t fl = g.sOn == 1 && g.N % 16 == 0 && g.sOr % 16 == 0 && (g.C == 1 || g.sOc % 16 == 0) && lenO % 16 == 0 ? IG2_OW : 0;
+      if (qa == IQ_PLANES) {
+        int si = -1;
+        for (size_t k = 0; k < i; k++) if (p.ops[k].out == o.in0) si = (int)k;
+        if (si < 0 || p.ops[(size_t)si].kind != IO_SOFTMAX || sole(o.in0, IO_GEMM2, (size_t)si) != (int)i) continue;
+        InferOp& sm = p.ops[(size_t)si];
+        if (g.C != sm.d[0] || g.R != sm.d[1] || g.K != sm.d[2] || g.sAm != 1 || g.sAr != g.K || g.sAc != g.R * g.K) continue;
+        const int64_t masked = infer_softmax_masked(p, sm);
+        fl |= IG2_SM | (infer_gemm2_rq_table_lds(sm.bits) ? IG2_SM_LDS : 0) | (masked == 0 ? IG2_SM_SKIP : 0);
+        InferConst& tc = p.consts[(size_t)sm.table];
+        if (tc.w8.empty()) { tc.w8.resize(tc.n * 2); for (size_t j = 0; j < tc.n; j++) { tc.w8[2 * j] = (int8_t)(tc.own[j] & 255); tc.w8[2 * j + 1] = (int8_t)(tc.own[j] >> 8); } }
+        sm.d[5] = i + 1; o.d[2] = (size_t)si;
+      } else if (qa != IQ_YES && qa != IQ_IF_INPUTS) continue;
+      o.fused[o.nfused++] = rq; o.d[1] = fl;
       continue;
     }
     if (o.kind != IO_GEMM || p.consts[(size_t)o.w].w8.empty()) continue;

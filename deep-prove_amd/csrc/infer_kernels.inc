@@ -906,13 +906,157 @@ __global__ __launch_bounds__(256) void k_infer_softmax(const int64_t* __restrict
   const int64_t v = x[i], lim = int64_t(1) << 24;
   infer_flag(v < -lim || v > lim, i, per, status, INFER_BAD_SOFTMAX);
   const int64_t masked = j <= row % R ? (int64_t)((uint64_t)v * (uint64_t)scalar + (uint64_t)shift[row]) : neg_inf;
-  int64_t r = masked < 0 ? (int64_t)(0 - (uint64_t)masked) : masked;
-  r >>= 16;
-  int64_t acc = table[r & ((int64_t(1) << tv) - 1)];
-  r >>= tv;
-  for (unsigned z = 0; z < zc; z++) { acc *= (r & ((int64_t(1) << zv) - 1)) == 0 ? 1 : 0; r >>= zv; }
+  size_t idx;
+  const bool keep = infer_softmax_index(masked, tv, zc, zv, &idx);  // (the one place of this arithmetic: k_infer_gemm2_i8_rq and the planner call it too)
+  const int64_t acc = keep ? table[idx] : 0;
   o[i] = acc;
   infer_put_forms(acc, i, nullptr, lo, hi);  // (the planner has seen every table entry within 0..16383)
+}
+// The product of two tensors of the batch with the Requant behind it — and, under SM, the Softmax in front of it — in ONE launch (infer_fuse_plan;
+// Q K^T -> Requant and Softmax -> probabilities x V -> Requant of an attention block). The work split is k_infer_gemm2_i8's: a workgroup of 4 waves
+// owns one 64 x 64 tile of ONE (sample, concat index), blockIdx.x = ((b * C + c) * tiles of R + tile of r) * tiles of N + tile of n; a wave holds
+// one 32 x 32 accumulator on v_mfma_i32_32x32x32_i8 (SM: two, the lo and hi planes over the same B fragment), and a wave whose block lies outside
+// R x N multiplies nothing. flags = InferOp::d[0] | d[1] (IG2_*).
+// Staging: K slices of IG_TK through LDS at pitch IG_LD; the NEXT slice is loaded into registers right behind the barrier that publishes the
+//   current one (k_infer_gemm_i8_rq's scheme) and is in flight while the current one is multiplied.
+//   SM = false: both operands are int8 copies, read by infer_g2_load in every layout of infer_gemm2_plan.
+//   SM = true: the left operand is MADE on the way into LDS. Thread t holds 16 consecutive int64 scores of tile row t >> 2 (k = k0 + 16 * (t & 3)
+//   ...; eight 16-byte loads where K % 16 == 0, words inside the row otherwise) and the row's shift, and applies k_infer_softmax's arithmetic
+//   through the same function: mask j <= row % R (the row of the Softmax is (b * C + c) * R + r: row % R = r), x * scalar + shift in unsigned 64-bit, the absolute
+//   value, >> 16, the table index masked to tv bits, the zero chunks (infer_softmax_index). Each value v (0..16383) is split into lo = v & 127 and
+//   hi = v >> 7; 16 bytes of each go to LDS in two 16-byte stores. Neither the int64 probabilities nor their planes exist in memory. Scores beyond
+//   R or K are not read and stand as zeros: whatever the table makes of them meets a zero of B (k >= K) or a row that is never stored (r >= R).
+//   The exponential table is read as 16-bit entries (every entry is within 0..16383): IG2_SM_LDS — the planner's decision, infer_gemm2_rq_table_lds —
+//   stages all 2^tv of them in dynamic LDS once per workgroup, otherwise they are gathered from the 16-bit image in global memory.
+// Causal skip (IG2_SM_SKIP: the planner has evaluated the value of a masked element, neg_inf through the table and the zero chunks, and found 0):
+//   a slice with k0 > r0 + 63 lies wholly above the diagonal of the tile's rows; the loop ends in front of it, loads included.
+// Epilogue: v = (int64)acc_hi * 128 + acc_lo (SM) or (int64)acc, then k_infer_requant's arithmetic letter for letter: |v| > 2^bits refuses the
+//   sample, (v * mult + 2^(sh-1)) >> sh in unsigned 64-bit with an arithmetic shift, clamp to +-127. One ballot per wave; only a wave with a bad
+//   element calls infer_refuse (the tile belongs to ONE sample). Rows >= R and columns >= N are never tested, stored or flagged. The int8 tile goes
+//   through LDS (the operand buffers are free behind a barrier after the last slice) and leaves at the output strides sOc, sOr, sOn — the result
+//   permutation of a ConcatMatMul included —, in 16-byte vectors along n under IG2_OW, bytes otherwise; the int64 form only under W64
+//   (infer_needs_int64). A refused sample's output is clamped like any other.
+// Refusal order: the Softmax's range test (|x| > 2^24) is DROPPED here. The host's shift step in front of this launch has applied it to every
+//   sample not refused before (infer_softmax_shifts: the status word is set, the shifts are zero), so when this kernel runs the word of such a
+//   sample already holds INFER_BAD_SOFTMAX or an earlier class, and the Requant refusal below — a compare-and-swap from zero — cannot replace it:
+//   the status word still names the FIRST node that refused the sample.
+struct InferSmArgs { const int64_t* x; const int64_t* shift; const uint16_t* tab; size_t lenX, lenS; int64_t scalar, neg_inf; unsigned tv, zc, zv; };
+template <bool SM, bool W64> __global__ __launch_bounds__(256) void k_infer_gemm2_i8_rq(const int8_t* __restrict__ A, size_t lenA, InferSmArgs sm, const int8_t* __restrict__ B, size_t lenB, int8_t* __restrict__ O8,
+                                                                                       int64_t* __restrict__ O64, size_t lenO, InferGemmShape g, unsigned tr, unsigned tn, unsigned flags, int64_t mult, unsigned sh,
+                                                                                       unsigned bits, unsigned* status) {
+  constexpr int PLANE = IG_TM * IG_LD;
+  __shared__ __attribute__((aligned(16))) int8_t lds[(SM ? 3 : 2) * PLANE];
+  extern __shared__ __attribute__((aligned(16))) uint16_t infer_sm_tab[];  // (IG2_SM_LDS: 2^tv entries)
+  static_assert(IG_TM * RQ_LDC <= 2 * PLANE && 3 * PLANE == (int)IG2_RQ_OPERANDS && IG_TM == 64 && IG_TN == 64 && IG_TK == 64, "the result tile lies in the operand buffers; a thread stages 16 k of one row");
+  int8_t* As = lds; int8_t* Bs = lds + (SM ? 2 : 1) * PLANE; int8_t* Cs = lds;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned t = blockIdx.x;
+  const size_t n0 = (size_t)(t % tn) * IG_TN; t /= tn;
+  const size_t r0 = (size_t)(t % tr) * IG_TM; t /= tr;
+  const size_t c = t % (unsigned)g.C, b = t / (unsigned)g.C;
+  const int8_t* Am = SM ? nullptr : A + b * lenA + c * g.sAc;
+  const int8_t* Bm = B + b * lenB + c * g.sBc;
+  const bool a_k = !(flags & IG2_AT), b_k = !(flags & IG2_BT), a_w = flags & IG2_AW, b_w = flags & IG2_BW, tab_lds = flags & IG2_SM_LDS;
+  const size_t sAr = a_k ? g.sAr : 1, sAm = a_k ? 1 : g.sAm, sBn = b_k ? g.sBn : 1, sBm = b_k ? 1 : g.sBm;  // (the unit stride as a constant)
+  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
+  const bool live = r0 + wm < g.R && n0 + wn < g.N;  // (uniform in the wave)
+  const size_t kend = SM && (flags & IG2_SM_SKIP) && r0 + IG_TM < g.K ? r0 + IG_TM : g.K;
+  // SM: this thread's row of scores and its shift
+  const size_t srow = r0 + (size_t)(tid >> 2), sk = (size_t)(tid & 3) * 16;
+  const bool row_in = SM && srow < g.R, k16 = (g.K & 15) == 0;
+  const int64_t* xr = SM ? sm.x + b * sm.lenX + (c * g.R + (row_in ? srow : 0)) * g.K : nullptr;
+  const int64_t shift = row_in ? sm.shift[b * sm.lenS + c * g.R + srow] : 0;
+  if (SM && tab_lds) {  // 2^tv 16-bit entries, tv >= 3: whole 16-byte vectors (published by the first barrier of the loop below... and one here)
+    const unsigned nv = (2u << sm.tv) >> 4;
+    for (unsigned i = (unsigned)tid; i < nv; i += 256) ((infer_v4i*)infer_sm_tab)[i] = ((const infer_v4i*)sm.tab)[i];
+    __syncthreads();
+  }
+  infer_v16i acc, acc2;
+#pragma unroll
+  for (int r = 0; r < 16; r++) acc[r] = acc2[r] = 0;
+  infer_v4i a = {0, 0, 0, 0}, a2 = {0, 0, 0, 0}, bb;
+  int64_t raw[16];
+  auto fetch = [&](size_t k0) {  // the slice at k0 into registers: zeros, and no load, beyond the matrices
+    bb = infer_g2_load(Bm, g.N, g.K, sBn, sBm, n0, k0, b_w, tid);
+    if (!SM) { a = infer_g2_load(Am, g.R, g.K, sAr, sAm, r0, k0, a_w, tid); return; }
+    const size_t k = k0 + sk;
+#pragma unroll
+    for (int j = 0; j < 16; j++) raw[j] = 0;
+    if (!row_in || k >= g.K) return;
+    if (k16) {
+#pragma unroll
+      for (int j = 0; j < 8; j++) { const infer_v2l v = *(const infer_v2l*)(xr + k + 2 * j); raw[2 * j] = v[0]; raw[2 * j + 1] = v[1]; }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; j++) if (k + j < g.K) raw[j] = xr[k + j];
+    }
+  };
+  auto make = [&](size_t k0, const uint16_t* tab) {  // raw -> the 16 bytes of each plane
+    const size_t k = k0 + sk;
+    unsigned lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const int64_t masked = k + j <= srow ? (int64_t)((uint64_t)raw[j] * (uint64_t)sm.scalar + (uint64_t)shift) : sm.neg_inf;
+      size_t idx;
+      const bool keep = infer_softmax_index(masked, sm.tv, sm.zc, sm.zv, &idx);
+      const unsigned v = keep ? (unsigned)tab[idx] : 0u;
+      lo[j >> 2] |= (v & 127u) << (8 * (j & 3)); hi[j >> 2] |= (v >> 7) << (8 * (j & 3));
+    }
+    a[0] = (int)lo[0]; a[1] = (int)lo[1]; a[2] = (int)lo[2]; a[3] = (int)lo[3];
+    a2[0] = (int)hi[0]; a2[1] = (int)hi[1]; a2[2] = (int)hi[2]; a2[3] = (int)hi[3];
+  };
+  fetch(0);
+  for (size_t k0 = 0; k0 < kend; k0 += IG_TK) {
+    if (SM) { if (tab_lds) make(k0, infer_sm_tab); else make(k0, sm.tab); }
+    __syncthreads();  // (the fragments of the slice before have been read)
+    infer_g2_store(As, a, SM || a_k, tid);
+    if (SM) infer_g2_store(As + PLANE, a2, true, tid);
+    infer_g2_store(Bs, bb, b_k, tid);
+    __syncthreads();
+    if (k0 + IG_TK < kend) fetch(k0 + IG_TK);
+    if (live) {
+#pragma unroll
+      for (int s = 0; s < IG_TK / 32; s++) {
+        if (k0 + s * 32 < g.K) {  // (uniform)
+          const int at = (wm + (lane & 31)) * IG_LD + s * 32 + (lane >> 5) * 16;
+          const infer_v4i fb = *(const infer_v4i*)&Bs[(wn + (lane & 31)) * IG_LD + s * 32 + (lane >> 5) * 16];
+          acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(*(const infer_v4i*)&As[at], fb, acc, 0, 0, 0);
+          if (SM) acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(*(const infer_v4i*)&As[PLANE + at], fb, acc2, 0, 0, 0);
+        }
+      }
+    }
+  }
+  __syncthreads();  // (every wave has read its last fragments: the operand buffers become the result tile)
+  const size_t col = n0 + wn + (lane & 31);
+  const uint64_t lim = uint64_t(1) << bits;
+  unsigned bad = 0;
+#pragma unroll
+  for (int r = 0; r < 16; r++) {
+    const int trow = wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    const int64_t v = SM ? (int64_t)acc2[r] * 128 + acc[r] : (int64_t)acc[r];
+    const uint64_t mag = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
+    if (mag > lim && r0 + trow < g.R && col < g.N) bad |= 1u << r;
+    int64_t y = (int64_t)((uint64_t)v * (uint64_t)mult + (uint64_t(1) << (sh - 1))) >> sh;
+    y = y < -127 ? -127 : y > 127 ? 127 : y;
+    Cs[trow * RQ_LDC + wn + (lane & 31)] = (int8_t)y;
+  }
+  if (__ballot(bad != 0) && bad) infer_refuse(status, b, INFER_BAD_REQUANT);
+  __syncthreads();
+  const size_t obase = b * lenO + c * g.sOc;
+  if (flags & IG2_OW) {  // one 16-byte vector of a row per thread
+    const size_t row = r0 + (tid >> 2), cc = n0 + (tid & 3) * 16;
+    if (row < g.R && cc < g.N) *(infer_v4i*)(O8 + obase + row * g.sOr + cc) = *(const infer_v4i*)&Cs[(tid >> 2) * RQ_LDC + (tid & 3) * 16];
+  } else {
+    for (int i = tid; i < IG_TM * IG_TN; i += 256) {
+      const size_t row = r0 + (i >> 6), cc = n0 + (i & 63);
+      if (row < g.R && cc < g.N) O8[obase + row * g.sOr + cc * g.sOn] = Cs[(i >> 6) * RQ_LDC + (i & 63)];
+    }
+  }
+  if (!W64) return;
+  for (int i = tid; i < IG_TM * IG_TN; i += 256) {
+    const size_t row = r0 + (i >> 6), cc = n0 + (i & 63);
+    if (row < g.R && cc < g.N) O64[obase + row * g.sOr + cc * g.sOn] = Cs[(i >> 6) * RQ_LDC + (i & 63)];
+  }
 }
 // Logits::Argmax (argmax_rows): one wave per row of K words (rows counts samples x rows of a sample); lanes stride over the row and keep (value,
 // index) under "greater, or equal at a smaller index"; the pairs are reduced across the wave by the same rule, so the result is the FIRST maximum
@@ -1057,10 +1201,11 @@ static dim3 infer_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 // k_infer_gemm_i8 and k_infer_gemm_i8_rq, [IO_KINDS + 3]: those of k_infer_conv_i8, [IO_KINDS + 4]: those of k_infer_gemm2_i8 (all counted
 // under their kind as well), [IO_KINDS + 5]: those of k_infer_gemm_i8_rq, [IO_KINDS + 6]: the ops it absorbed — served, and counted under
 // their kinds, without a launch of their own —, [IO_KINDS + 7]: the launches of k_infer_conv_i8_rq (counted under [IO_KINDS + 3] as well; the ops
-// it absorbed under [IO_KINDS + 6]). fuse: the head of a chain (infer_fuse_plan) whose input has its int8 form in this call takes
+// it absorbed under [IO_KINDS + 6]), [IO_KINDS + 8]: the launches of k_infer_gemm2_i8_rq (counted under IO_GEMM2 and [IO_KINDS + 4] as well; its
+// Requant and, under SM, the Softmax it serves under [IO_KINDS + 6]). fuse: the head of a chain (infer_fuse_plan) whose input has its int8 form in this call takes
 // k_infer_gemm_i8_rq / k_infer_conv_i8_rq; the result is the number of ops absorbed (IO_GEMM: o.d[1], o.d[2], IO_CONV: o.fused — the caller skips
-// them), 0 for every other launch.
-constexpr size_t INFER_COUNTS = IO_KINDS + 8;
+// them; IO_GEMM2: o.fused[0], the Softmax of an SM chain has skipped its own launch), 0 for every other launch.
+constexpr size_t INFER_COUNTS = IO_KINDS + 9;
 static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferScratch& m, InferDeviceState* st, hipStream_t s, size_t nb, size_t* launches, bool fuse) {
   static const bool no_mfma = getenv("DP_INFER_NO_MFMA") && atoi(getenv("DP_INFER_NO_MFMA"));
   const bool i8 = infer_reads_int8_only(p, o, o.in0, m.q, nb, no_mfma);  // (the one predicate: also what infer_needs_int64 elides by)
@@ -1098,6 +1243,25 @@ static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferS
       const size_t tr = (o.g.R + IG_TM - 1) / IG_TM, tn = (o.g.N + IG_TN - 1) / IG_TN, tiles = infer_gemm2_tiles(o.g, nb);
       static_assert(IG_TM == 64 && IG_TN == 64, "infer_gemm2_tiles counts 64 x 64 tiles");
       // the planner found a form for both operands (o.d[0]); i8: both have their int8 form in this call — only the LEFT one may be two planes
+      if (const int form = fuse ? infer_gemm2_rq_form(p, o, m.q, nb, no_mfma) : 0) {  // the chain in one launch: o.fused[0] = its Requant; form 2: the Softmax o.d[2] as well
+        const InferOp& rq = p.ops[(size_t)o.fused[0]];
+        int64_t* o64 = infer_needs_int64(p, rq.out, m.q, nb, no_mfma) ? m.T64(rq.out) : nullptr;
+        const unsigned flags = (unsigned)(o.d[0] | o.d[1]);
+        InferSmArgs sa = {};
+        size_t lds = 0;
+        if (form == 2) {
+          const InferOp& sm = p.ops[o.d[2]];
+          sa = InferSmArgs{m.T64(sm.in0), m.T64(sm.in1), (const uint16_t*)infer_const8(p, st, sm.table), p.tensors[(size_t)sm.in0].len, p.tensors[(size_t)sm.in1].len, sm.left, infer_softmax_neg_inf(sm.right),
+                           sm.bits, (unsigned)sm.d[3], (unsigned)sm.d[4]};
+          DP_REQUIRE(!(flags & IG2_SM_LDS) || infer_gemm2_rq_table_lds(sm.bits), DP_ERR_ARG, "dp_model_infer: softmax table in LDS");
+          lds = (flags & IG2_SM_LDS) ? size_t(2) << sm.bits : 0;
+        }
+        auto go = [&](auto kern) { kern<<<dim3((unsigned)tiles), 256, lds, s>>>(form == 2 ? nullptr : m.T8(o.in0), lenA, sa, m.T8(o.in1), lenB, m.T8(rq.out), o64, p.tensors[(size_t)rq.out].len, o.g, (unsigned)tr, (unsigned)tn, flags, rq.left, rq.shift, rq.bits, m.status()); };
+        if (form == 2) { if (o64) go(k_infer_gemm2_i8_rq<true, true>); else go(k_infer_gemm2_i8_rq<true, false>); }
+        else { if (o64) go(k_infer_gemm2_i8_rq<false, true>); else go(k_infer_gemm2_i8_rq<false, false>); }
+        launches[IO_KINDS + 4]++; launches[IO_REQUANT]++; launches[IO_KINDS + 8]++; launches[IO_KINDS + 6] += 1 + (form == 2);
+        return 1;
+      }
       if (i8) {
         if (m.q[(size_t)o.in0] == IQ_PLANES) k_infer_gemm2_i8<true><<<dim3((unsigned)tiles), 256, 0, s>>>(m.TP(o.in0, 0), m.TP(o.in0, 1), lenA, m.T8(o.in1), lenB, m.T64(o.out), len, o.g, (unsigned)tr, (unsigned)tn, (unsigned)o.d[0]);
         else k_infer_gemm2_i8<false><<<dim3((unsigned)tiles), 256, 0, s>>>(m.T8(o.in0), nullptr, lenA, m.T8(o.in1), lenB, m.T64(o.out), len, o.g, (unsigned)tr, (unsigned)tn, (unsigned)o.d[0]);
@@ -1170,7 +1334,9 @@ static size_t infer_launch(const InferProgram& p, const InferOp& o, const InferS
       k_infer_layernorm<<<infer_grid(rows * 64), 256, 0, s>>>(m.T64(o.in0), c64(o.w), c64(o.bias), c64(o.table), m.T64(o.out), rows, o.d[0], (int64_t)o.d[1], o.left, o.shift, m.status(), len / o.d[0]);
       break;
     }
-    case IO_SOFTMAX: k_infer_softmax<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.in1), c64(o.table), m.T64(o.out), m.TP(o.out, 0), m.TP(o.out, 1), n, o.d[1], o.d[2], o.left, -(((o.right >> 16) + 1) << 16), o.bits, (unsigned)o.d[3], (unsigned)o.d[4], m.status(), len); break;  // (after infer_shift_trip)
+    case IO_SOFTMAX:
+      if (fuse && o.d[5] && infer_gemm2_rq_form(p, p.ops[o.d[5] - 1], m.q, nb, no_mfma) == 2) break;  // (served, after its shift step, by the k_infer_gemm2_i8_rq launch of its chain)
+      k_infer_softmax<<<infer_grid(n), 256, 0, s>>>(m.T64(o.in0), m.T64(o.in1), c64(o.table), m.T64(o.out), m.TP(o.out, 0), m.TP(o.out, 1), n, o.d[1], o.d[2], o.left, -(((o.right >> 16) + 1) << 16), o.bits, (unsigned)o.d[3], (unsigned)o.d[4], m.status(), len); break;  // (after infer_shift_trip)
     case IO_ARGMAX: { const size_t rows = nb * o.d[0]; k_infer_argmax<<<infer_grid(rows * 64), 256, 0, s>>>(m.T64(o.in0), i8 ? m.T8(o.in0) : nullptr, m.T64(o.out), rows, o.d[1]); break; }
     default: throw DpError(DP_ERR_ARG, "dp_model_infer: unknown op");
   }
@@ -1212,7 +1378,7 @@ static uint32_t infer_enqueue(const InferProgram& p, const InferScratch& m, Infe
       trips++; trip_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
       if (!checked) if (const uint32_t cls = infer_first_class(m.sm_status(), nb)) return cls;
     }
-    for (size_t k = infer_launch(p, o, m, st, s, nb, launches, fuse); k >= 1; k--) absorbed[o.kind == IO_CONV ? (size_t)o.fused[k - 1] : o.d[k]] = 1;
+    for (size_t k = infer_launch(p, o, m, st, s, nb, launches, fuse); k >= 1; k--) absorbed[o.kind == IO_GEMM ? o.d[k] : (size_t)o.fused[k - 1]] = 1;
   }
   return INFER_OK;
 }
@@ -1295,8 +1461,8 @@ void hip_infer_run(Dev* d, const InferProgram& p, InferDeviceState* st, const in
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (wall_ms) *wall_ms = ms;
   const size_t n_i8 = launches[IO_KINDS + 2] + launches[IO_KINDS + 4], n_i64 = launches[IO_GEMM] + launches[IO_GEMM2] - n_i8;
-  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu gemm2_i8 %zu conv %zu conv_i8 %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu argmax %zu fused %zu conv_rq %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s%s\n",
-                   n_i8, n_i64, launches[IO_KINDS + 4], launches[IO_CONV], launches[IO_KINDS + 3], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], launches[IO_ARGMAX], launches[IO_KINDS + 5], launches[IO_KINDS + 7], trips, trip_ms,
+  if (log_line) fprintf(stderr, "[dp infer] gemm_i8 %zu gemm_i64 %zu gemm2_i8 %zu conv %zu conv_i8 %zu requant %zu relu %zu add %zu add2 %zu embed %zu maxpool %zu load %zu store %zu gelu %zu layernorm %zu softmax %zu argmax %zu fused %zu conv_rq %zu gemm2_rq %zu shift_trips %zu shift_ms %.3f; batch %zu in %zu chunks of %zu, scratch %.1f MB, inputs as %s, %.3f ms%s%s\n",
+                   n_i8, n_i64, launches[IO_KINDS + 4], launches[IO_CONV], launches[IO_KINDS + 3], launches[IO_REQUANT], launches[IO_RELU], launches[IO_ADDC], launches[IO_ADD2], launches[IO_EMBED], launches[IO_MAXPOOL], launches[IO_KINDS], launches[IO_KINDS + 1], launches[IO_GELU], launches[IO_LAYERNORM], launches[IO_SOFTMAX], launches[IO_ARGMAX], launches[IO_KINDS + 5], launches[IO_KINDS + 7], launches[IO_KINDS + 8], trips, trip_ms,
                    ninputs, nchunks, chunk, (double)m.total / 1048576.0, m.in_q ? "int8" : "int64", ms,
                    taps ? ("; taps " + std::to_string(p.taps.size()) + " entries, " + std::to_string(p.row_words) + " words, pack_launches " + std::to_string(tap_launches) + " pack_ms " + std::to_string(tap_ms)).c_str() : "",
                    reasons ? ("; checked, refused " + std::to_string(nrefused)).c_str() : "");

@@ -37,7 +37,8 @@
  * Knobs (environment): DP_INFER_SCRATCH_MB (activation scratch of one chunk of the batch, default 1024), DP_INFER_NO_MFMA=1 (64-bit
  * products and convolutions everywhere), DP_INFER_NO_FUSE=1 (no k_infer_gemm_i8_rq and no k_infer_conv_i8_rq: a product, its Requant and a ReLU behind it are three
  * launches instead of one, a convolution, its Requant, a ReLU and a MaxPool behind it up to four; the log line's `fused N`, directly after `argmax N`, counts the launches of the first kernel and
- * `conv_rq N`, directly after it, those of the second), DP_INFER_LOG=1 (one `[dp infer]` line per call on stderr: launches per kernel, chunks, wall time; `gemm_i8 N`
+ * `conv_rq N`, directly after it, those of the second; `gemm2_rq N`, directly after that, the launches of k_infer_gemm2_i8_rq, which serves the product of
+ * two tensors, its Requant and, for probabilities x V, the Softmax in front of it, and which the same switch turns off), DP_INFER_LOG=1 (one `[dp infer]` line per call on stderr: launches per kernel, chunks, wall time; `gemm_i8 N`
  * counts every product that ran on the i8 MFMA, `gemm_i64 N` the others, and `gemm2_i8 N`, directly after it, those of the first that were
  * products of two tensors of the batch: a MatMul of two inputs, a ConcatMatMul and the two products of an Mha node take the matrix units when each
  * operand is contiguous along the summed axis or along its other matrix axis, K * 128 * 128 < 2^31, the right operand is within -128..127 (a

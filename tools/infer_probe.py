@@ -3,10 +3,11 @@ model and uploads the int8 weights), next to the wall time of the same inputs th
 threads — what a caller without the device entry point does on the CPUs a GPU box allows. Outputs of the two paths are compared.
 --all-kinds: dp_model_infer_ex with DP_INFER_ALL_KINDS (LayerNorm / Softmax / Mha / GELU models); the `[dp infer]` lines of the timed calls are
 read back (the library's stderr is redirected to a file) for the share of the wall time spent in the Softmax shift round trips.
-transformer_layer / transformer_layer_gelu: golden case 14's model (64 x 256, 4 heads of 64, ffn 1 024, config 66), without / with GELU.
+transformer_layer / transformer_layer_gelu: golden case 14's model (64 x 256, 4 heads of 64, ffn 1 024, config 66), without / with GELU;
+transformer_block: its attention half with the Mha node as separate nodes (Q K^T -> Requant -> Softmax -> probabilities x V -> Requant).
 --checked: dp_model_infer_checked (a status per input) timed beside the plain call on the same inputs, the two alternating call by call; its
 outputs must be the plain call's and no input may be refused.
-usage: python tools/infer_probe.py dense_4m|cnn_264k|transformer_layer[_gelu]|<model of deep_prove_amd.models> <batch> <repeats> [--all-kinds] [--checked]"""
+usage: python tools/infer_probe.py dense_4m|cnn_264k|transformer_layer[_gelu]|transformer_block|<model of deep_prove_amd.models> <batch> <repeats> [--all-kinds] [--checked]"""
 import os, re, subprocess, sys, tempfile, time
 from concurrent.futures import ThreadPoolExecutor
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
@@ -20,7 +21,8 @@ argv = [a for a in sys.argv if a not in ("--all-kinds", "--checked")]
 wl = argv[1]; batch = int(argv[2]); reps = int(argv[3]) if len(argv) > 3 else 5
 if all_kinds:  # (read once per process, at the first call)
     os.environ["DP_INFER_LOG"] = "1"
-mb = dpa.models.transformer_layer(64, 256, 4, 64, 1024, config=66, gelu=wl.endswith("_gelu")) if wl.startswith("transformer_layer") else getattr(dpa.models, wl)()
+mb = (dpa.models.transformer_layer(64, 256, 4, 64, 1024, config=66, gelu=wl.endswith("_gelu")) if wl.startswith("transformer_layer") else
+      dpa.models.transformer_block(64, 256, 4, 64, config=66) if wl == "transformer_block" else getattr(dpa.models, wl)())
 blob = mb.blob()
 xs = np.stack([mb.input(3000 + i) for i in range(batch)])
 dev = dpa.Device(0)
